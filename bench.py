@@ -10,10 +10,21 @@ LDA.jl:201-209, MMCTM.jl:462-479, IMMCTM.jl:440-451) over one batch of synthetic
   --scaling weak        (default) every rank holds its own corpus of the configuration's size
   --scaling strong      the ONE corpus of the configuration's size, documents sharded over the ranks (balanced by nonzeros)
 
-The default invocation (config 2) also measures configs 4 and 5 for a bounded number of steps, and config 2's model on 640k documents
-per GPU, and attaches them to the same JSON line under "also" (--no-also switches that off); the headline keys are config 2's.
+A plain run (no --full) does only what the headline needs: corpus and model, W warm-up steps, ONE timed region of exactly K steps (unless
+--repeats asks for more), --dump-outputs if given, and a short JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+run's shape).  Everything else is measured with --full only: the per-phase kernel spans, the roofline, the HIP-event timing, the parity
+probes against the oracle, the CPU baselines, every other all-reduce transport, and -- for the default invocation -- the entries below.
 
-N > 1, default invocation: the headline stays config 2 weak (10k documents per GPU) on the default transport, and the line also carries
+  --dump-outputs DIR    after the timed steps, the state the last of them left (what a caller of the timed path reads back: LDA
+                        lambda, Elnbeta, gamma, theta, phi; MMCTM / IMMCTM mu, Sigma, gamma, lambda, nu, zeta, theta; both the timed
+                        steps' log-likelihoods as ll) as DIR/<name>.npy in float64; an array of more than DUMP_CAP_VALUES values is
+                        written as a fixed, seeded sample of its rows.  Same arguments, same inputs.
+
+--full, default invocation (config 2): also configs 4 and 5 for a bounded number of steps, config 2's model on 640k documents per GPU, and
+at N = 1 the BRCA restart sweep and the shard proxy, attached to the same JSON line under "also" (--no-also switches that off); the
+headline keys are config 2's.
+
+--full, N > 1, default invocation: the headline stays config 2 weak (10k documents per GPU) on the default transport, and the line also carries
   "strong"           config 2's ONE 10k-document corpus sharded over the N ranks (the literal ">= 6x at 8 GPUs" target of BASELINE.json)
   also.cfg4 / cfg5   the 50k / 100k-document corpus SHARDED over the N ranks (strong: that is BASELINE configs[3] / configs[4]), each with
                      a "weak" entry (every rank its own 50k / 100k corpus) beside it
@@ -29,8 +40,8 @@ share a card (more ranks than devices: a one-card rehearsal of the N > 1 path) t
 up from host-exchanged IPC handles -- RCCL refuses two ranks on one device.
 
 Contract: W untimed warm-up steps, then exactly K steps bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over
-ranks.  That timed region is repeated R times (--repeats, default 9): `ms_per_step` / `value` are the MEDIAN region, min / max beside
-them (a 20-step region of config 2 lasts 0.4 ms; one region alone carries the +-40 us of the bracketing synchronisations).
+ranks.  That timed region is repeated R times (--repeats; default 1, with --full 9): `ms_per_step` / `value` are the MEDIAN region, min /
+max beside them (a 20-step region of config 2 lasts 0.4 ms; one region alone carries the +-40 us of the bracketing synchronisations).
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -434,14 +445,52 @@ def make_corpus(cfg_id, D, seed):
 
 _CORPORA = {}
 
+DUMP_CAP_VALUES = 1 << 19      # --dump-outputs: at most 4 MiB of float64 per array (eight arrays at most: 32 MiB in all)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_rows(a):
+    """`a` as float64; above DUMP_CAP_VALUES values, the rows of a seeded random sample (sorted; it depends on the array's shape only)"""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.size <= DUMP_CAP_VALUES:
+        return a
+    keep = max(1, DUMP_CAP_VALUES // max(a.size // a.shape[0], 1))
+    return a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], size=keep, replace=False))]
+
+
+def dump_outputs(env, cfg, model, steps, out_dir):
+    """--dump-outputs: what the timed path left after its last step, read back through the model's accessors as a caller would, written by
+    rank 0 as out_dir/<name>.npy.  Every rank makes the same calls: reading the log-likelihood history ends in the ranks' exchange."""
+    np, pkg, ctx = env.np, env.pkg, env.ctx
+    lib, C = pkg.lib(), pkg._lib.C
+    n = C.c_int()
+    if cfg["model"] == "lda":
+        ll = np.zeros(steps)
+        pkg._lib.check(lib.mmm_lda_ll_history(model._h, ll.ctypes.data, steps, C.byref(n)), ctx.h, "mmm_lda_ll_history")
+        out = {"ll": ll[:n.value], "lambda": model.λ, "Elnbeta": model.Elnβ, "gamma": model.γ.T, "theta": model.θ.T, "phi": model.phi_flat()}
+    else:
+        D, M, MK = model.D, model.M, model.MK
+        ll = np.zeros(steps * M)
+        pkg._lib.check(lib.mmm_ctm_ll_history(model._h, ll.ctypes.data, steps, C.byref(n)), ctx.h, "mmm_ctm_ll_history")
+        out = {"ll": ll[:n.value * M].reshape(n.value, M), "mu": model._get("mu"), "Sigma": model._get("Sigma").reshape(MK, MK),
+               "gamma": model._get("gamma"), "lambda": model._get("lambda").reshape(D, MK), "nu": model._get("nu").reshape(D, MK),
+               "zeta": model._get("zeta").reshape(D, M), "theta": model._get("theta")}
+    if env.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(out_dir, name + ".npy"), dump_rows(a))
+
 
 def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline, cpu_target_s=None, every_transport=False, probe=True,
-               proxy_shard=0, corpus=None):
+               proxy_shard=0, corpus=None, full=True, dump_dir=None):
     """Measure one configuration on the ranks of `env`; rank 0 gets the result dictionary, the others None.  every_transport (N > 1): after
     the full measurement on the current all-reduce transport, the timed regions once more on every other transport the job can run, on a
     fresh model over the same shard, under res["transports"].  proxy_shard = N (one GPU): the model runs over rank 0's shard of an N-rank
     strong run of the corpus (`shard_documents(X, N, 0)`), no communicator -- the per-GPU work of that run without its exchange
-    (shard_proxy).  corpus = (X, init): use this corpus instead of generating one."""
+    (shard_proxy).  corpus = (X, init): use this corpus instead of generating one.  full=False: the timed regions and the line's headline
+    keys only (no event timing, phase spans, roofline, probes, CPU baseline or other transports).  dump_dir: dump_outputs() right after the
+    timed regions."""
     np, pkg, ctx, world, rank = env.np, env.pkg, env.ctx, env.world, env.rank
     import np_ref
     cfg = CONFIGS[cfg_id]
@@ -523,6 +572,42 @@ def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline,
     regions = timed_regions(run)
     dt = float(np.median(regions))
     note("timed regions done (%.4f ms per step, all-reduce: %s)" % (dt / steps * 1e3, primary))
+    if dump_dir:
+        dump_outputs(env, cfg, model, steps, dump_dir)
+
+    def headline():
+        """on every rank (the gathers are collective); rank 0 gets the line's headline keys and its config, the others None"""
+        transports = env.allgather_obj(ctx.transport)
+        nranks_seen = env.allgather_obj(int(lib.mmm_comm_nranks(ctx.h)))
+        docs_per_rank = env.allgather_obj(D)
+        if rank != 0:
+            return None
+        docs_step = sum(docs_per_rank)
+        res = {
+            "metric": "E-step docs/sec", "value": docs_step * steps / dt, "unit": "docs/s", "n_gpus": world,
+            "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
+            "ms_per_step_min": min(regions) / steps * 1e3, "ms_per_step_max": max(regions) / steps * 1e3, "repeats": len(regions),
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": (cfg["name"] % Dcfg) + (" per GPU" if scaling == "weak" and world > 1 else "") +
+                                   ", nnz(rank 0)=%d, one EM iteration per step" % nnz,
+                       "docs_rank0": D, "docs_total": docs_step, "docs_per_rank": docs_per_rank, "terms": V, "topics": K,
+                       "sharding": "docs x%d (%s)" % (world, scaling), "allreduce": ctx.transport, "allreduce_per_rank": transports,
+                       "comm_nranks": nranks_seen[0], "comm_nranks_per_rank": nranks_seen,
+                       "devices_visible": env.ndev, "ranks_share_a_card": bool(env.shared_card)},
+        }
+        if scaling == "strong" and world > 1:
+            res["config"]["note"] = ("strong scaling of a %d-document corpus: the per-iteration exchange has a fixed latency of the order of the "
+                                     "iteration itself, so the 10k-document LDA corpus cannot speed up 6x on 8 GPUs; weak scaling is the "
+                                     "curve that can" % Dcfg)
+        return res
+
+    if not full:
+        res = headline()
+        if res is not None:
+            res["timing_note"] = ("ms_per_step: wall clock over the K timed steps between barrier + device synchronisation on both sides, median "
+                                  "of %d region(s); per-phase, event, roofline, parity and CPU-baseline figures: --full" % len(regions))
+        model.close()
+        return res
     try:
         ev_regions = event_regions(run)
     except Exception as e:       # noqa: BLE001 -- an extra: the contract's figure does not depend on it
@@ -571,18 +656,9 @@ def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline,
         ll = np.zeros(1); n = pkg._lib.C.c_int()
         pkg._lib.check(lib.mmm_lda_ll_history(model._h, ll.ctypes.data, 1, pkg._lib.C.byref(n)), ctx.h)
         ll_last = float(ll[0])
-    transports = env.allgather_obj(ctx.transport)
-    nranks_seen = env.allgather_obj(int(lib.mmm_comm_nranks(ctx.h)))
-    docs_per_rank = env.allgather_obj(D)
-    res = None
+    res = headline()
     if rank == 0:
-        docs_step = sum(docs_per_rank)
-        ms_step = dt / steps * 1e3
-        res = {
-            "metric": "E-step docs/sec", "value": docs_step * steps / dt, "unit": "docs/s", "n_gpus": world,
-            "steps": steps, "warmup": warmup, "ms_per_step": ms_step,
-            "ms_per_step_min": min(regions) / steps * 1e3, "ms_per_step_max": max(regions) / steps * 1e3, "repeats": len(regions),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        res.update({
             "ms_per_step_events": (float(np.median(ev_regions)) / steps * 1e3) if ev_regions else None,
             "ms_per_step_events_min": (min(ev_regions) / steps * 1e3) if ev_regions else None,
             # (LDA: every pass does the same work, the two kinds of regions are comparable; a CTM fit's later passes need fewer LD_MMA
@@ -594,17 +670,7 @@ def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline,
                             "is several per cent of the region" + ("" if cfg["model"] == "lda" else ".  CTM: the event regions are the passes AFTER the wall-clock "
                             "regions of the same fit (passes %d-%d against %d-%d), whose solves need fewer evaluations -- the two figures are not the same work" % (
                                 warmup + len(regions) * steps + 1, warmup + 2 * len(regions) * steps, warmup + 1, warmup + len(regions) * steps))) if ev_regions else ("event timing unavailable: " + ev_error),
-            "config": {"workload": (cfg["name"] % Dcfg) + (" per GPU" if scaling == "weak" and world > 1 else "") +
-                                   ", nnz(rank 0)=%d, one EM iteration per step" % nnz,
-                       "docs_rank0": D, "docs_total": docs_step, "docs_per_rank": docs_per_rank, "terms": V, "topics": K,
-                       "sharding": "docs x%d (%s)" % (world, scaling), "allreduce": ctx.transport, "allreduce_per_rank": transports,
-                       "comm_nranks": nranks_seen[0], "comm_nranks_per_rank": nranks_seen,
-                       "devices_visible": env.ndev, "ranks_share_a_card": bool(env.shared_card)},
-        }
-        if scaling == "strong" and world > 1:
-            res["config"]["note"] = ("strong scaling of a %d-document corpus: the per-iteration exchange has a fixed latency of the order of the "
-                                     "iteration itself, so the 10k-document LDA corpus cannot speed up 6x on 8 GPUs; weak scaling is the "
-                                     "curve that can" % Dcfg)
+        })
         res["iteration"] = {"kernel_us": phases, "sum_kernel_us": sum(phases.values()), "step_us": step_us_profiled,
                             "kernel_fraction_of_step": sum(phases.values()) / step_us_profiled if step_us_profiled > 0 else None,
                             "timing": "HIP-event spans per phase of the pass (mmm_ctx_profile_select) in repeats of the timed K steps; LDA: one phase per "
@@ -737,7 +803,7 @@ def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline,
         entries = {}
         if rank == 0:
             entries[primary] = {"value": res["value"], "ms_per_step": res["ms_per_step"], "ms_per_step_min": res["ms_per_step_min"],
-                                "allreduce_per_rank": transports, "roofline_frac_per_gpu": res["roofline"]["frac"],
+                                "allreduce_per_rank": res["config"]["allreduce_per_rank"], "roofline_frac_per_gpu": res["roofline"]["frac"],
                                 "hbm_roofline_frac_per_gpu": res["roofline"].get("hbm", res["roofline"])["frac"]}
         for name, switch in transports_avail[1:]:
             switch()
@@ -751,7 +817,7 @@ def run_config(env, cfg_id, scaling, steps, warmup, repeats, docs, cpu_baseline,
             d2 = float(np.median(reg2))
             note("transport %s: %.4f ms per step" % (name, d2 / steps * 1e3))
             if rank == 0:
-                entries[name] = {"value": sum(docs_per_rank) * steps / d2, "ms_per_step": d2 / steps * 1e3, "ms_per_step_min": min(reg2) / steps * 1e3,
+                entries[name] = {"value": res["config"]["docs_total"] * steps / d2, "ms_per_step": d2 / steps * 1e3, "ms_per_step_min": min(reg2) / steps * 1e3,
                                  "allreduce_per_rank": tr2,
                                  "roofline_frac_per_gpu": res["roofline"]["frac"], "hbm_roofline_frac_per_gpu": res["roofline"].get("hbm", res["roofline"])["frac"],
                                  "note": "timed regions only; the dominant kernel is the same launch as on the primary transport (its fraction is repeated)"}
@@ -877,10 +943,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--repeats", type=int, default=9, help="timed regions of --steps iterations each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps iterations each; the median is reported (default 1, "
+                                                                  "with --full 9)")
     ap.add_argument("--docs", type=int, default=0, help="documents per GPU (weak) / in total (strong); default: the configuration's size")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="default invocation only: do not attach configs 4 and 5 under \"also\"")
+    ap.add_argument("--full", action="store_true", help="also every figure beyond the headline: event timing, phase spans, roofline, parity "
+                                                        "probes, CPU baselines, other transports and (default invocation) the \"also\" entries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the last timed step left as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full, default invocation only: do not attach configs 4 and 5 under \"also\"")
     ap.add_argument("--launch-timeout", type=int, default=1500, help="self-launched --gpus N: seconds before the ranks are killed")
     ap.add_argument("--lda-build", choices=["auto", "sparse", "dense", "wide"], default="auto", help="mmm_tuning_opts.lda_build of the LDA handles (A/B runs)")
     ap.add_argument("--ctm-build", choices=["auto", "sparse", "dense", "wide"], default="auto", help="mmm_tuning_opts.ctm_build of the CTM handles (A/B runs)")
@@ -892,16 +962,18 @@ def main():
         args.steps = 50 if cfg["model"] == "lda" else 10
     if args.warmup is None:
         args.warmup = 5 if cfg["model"] == "lda" else 2
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
 
     env = Env(args.gpus)
     if args.lda_build != "auto" or args.ctm_build != "auto":
         env.ctx.set_tuning(lda_build=args.lda_build, ctm_build=args.ctm_build)
     multi = env.world > 1
     # (MMM_FORCE_RCCL=1 MMM_P2P_ONE_RANK=1 at N = 1: a one-rank communicator with mailboxes -- the transport switch rehearsed on one GPU)
-    res = run_config(env, args.config, args.scaling, args.steps, args.warmup, args.repeats, args.docs, not args.no_cpu_baseline,
-                     every_transport=multi or env.has_comm)
+    res = run_config(env, args.config, args.scaling, args.steps, args.warmup, args.repeats, args.docs, args.full and not args.no_cpu_baseline,
+                     every_transport=args.full and (multi or env.has_comm), probe=args.full, full=args.full, dump_dir=args.dump_outputs)
     # the other two throughput configurations of BASELINE.json, bounded, on the same ranks, in the same line
-    if args.config == 2 and not args.docs and not args.no_also:
+    if args.full and args.config == 2 and not args.docs and not args.no_also:
         def attempt(fn):
             try:
                 return fn()

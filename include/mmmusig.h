@@ -232,6 +232,33 @@ int mmm_lda_fit(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_ite
 int mmm_lda_infer(mmm_lda* m, int unsmoothed, int maxiter, double tol, double* ll_hist, int* n_iter,
                   int* converged);
 
+/* LDA restart batching -- LDA's constructor draws its topics at random (rand(1:100, V, K), LDA.jl:36), so users run several restarts
+ * and keep the best.  A batch handle holds R >= 1 LDA models ("replicas") over ONE resident corpus; replica r is created from
+ * lambda0[r] (R contiguous V*K blocks, each as in mmm_lda_create).  The batched fit advances all replicas with one launch per kernel
+ * (replica on grid.y) of the split pipeline: the E-step build of the shape, the reduction with its ll blocks, the M-step with its pass
+ * tail.  Contract:
+ *   - replica r computes, bit for bit, what a single handle created from lambda0[r] computes under the same mmm_tuning_opts plus
+ *     MMM_OFF_LDA_MERGED over a whole fit!: ll history, pass count, converged, ELBO and every field;
+ *   - its bits do not depend on R or on the other replicas: the launch geometry that fixes the order of the sums comes from D (and
+ *     geometry_cus) alone;
+ *   - each replica stops by its own rule (LDA.jl:215 + common.jl:53-56, evaluated on the device as in the single fit); later passes
+ *     are no-ops for it.  The batch ends when every replica has stopped or after maxiter passes.
+ * R = 1 is exactly mmm_lda_create (merged launch included).  MMM_ERR_UNSUPPORTED, with the limit in the message, for R > 1 on shapes
+ * whose single handle takes the wide path (lda_build = MMM_BUILD_WIDE, K >= 25 under MMM_BUILD_AUTO, tables beyond LDS) and on a
+ * context with a communicator (deal restarts over ranks on the host); MMM_ERR_ARG for R < 1.  ILDA has no batches
+ * (mmm_lda_fit_batch on an ILDA handle: MMM_ERR_UNSUPPORTED).
+ * On a handle with R > 1: mmm_lda_get (every field), mmm_lda_ll_history, mmm_lda_elbo and mmm_lda_events act on the selected replica
+ * (0 after create; theta and phi are one buffer, formed for it on demand); mmm_lda_geometry and mmm_lda_destroy work as on any
+ * handle; set, set_hyper, the update_* stages, loglik, iterate, fit and infer return MMM_ERR_UNSUPPORTED and leave the handle as it was. */
+int mmm_lda_create_batch(mmm_ctx* ctx, int R, int D, int V, int K, double alpha, double eta, const int64_t* doc_ptr,
+                         const int32_t* term, const int32_t* count, const double* lambda0, mmm_lda** out);
+int mmm_lda_replicas(const mmm_lda* m);
+int mmm_lda_select(mmm_lda* m, int r);
+/* fit! of every replica.  ll_hist: [R][maxiter] (replica-major, n_iter[r] values each) or NULL; n_iter, converged: [R]; elbo: [R] or
+ * NULL.  Replicas that reach maxiter get mmm_lda_fit's final convergence test.  All replicas must stand at the same pass (a fresh
+ * batch, or one whose earlier fit ran every replica to maxiter). */
+int mmm_lda_fit_batch(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged, double* elbo);
+
 /* ---- MMCTM (src/MMCTM.jl) and IMMCTM (src/IMMCTM.jl) -------------------------------------------------------- */
 typedef struct {
     double xtol_rel;     /* 1e-4   MMCTM.jl:129,158 */

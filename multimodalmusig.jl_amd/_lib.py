@@ -112,6 +112,10 @@ _SIGS = {
     "mmm_ctm_replicas": (C.c_int, [vp]),
     "mmm_ctm_select": (C.c_int, [vp, C.c_int]),
     "mmm_ctm_fit_batch": (C.c_int, [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]),
+    "mmm_lda_create_batch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, i64p, vp, vp, f64p, C.POINTER(vp)]),
+    "mmm_lda_replicas": (C.c_int, [vp]),
+    "mmm_lda_select": (C.c_int, [vp, C.c_int]),
+    "mmm_lda_fit_batch": (C.c_int, [vp, C.c_int, C.c_double, vp, vp, vp, vp]),
     "mmm_tuning_opts_default": (None, [vp]),
     "mmm_ctx_set_tuning": (C.c_int, [vp, vp]),
     "mmm_ctx_get_tuning": (C.c_int, [vp, vp]),

@@ -79,6 +79,12 @@ struct LdaCtl {
 
 struct Ring { double* s[3]; };
 
+// Batch handles (mmm_lda_create_batch): every per-model array holds R replicas back to back (replica-major), and the launches of a
+// batched pass carry the replica on grid.y.  rep<RB>(p, n) is replica blockIdx.y's copy of an array of n elements per replica in a
+// kernel built for batches, p itself otherwise -- the single-model builds compile to the code they had before batches existed.
+template <bool RB, class T>
+__device__ __forceinline__ T* rep(T* p, size_t n) { return RB ? p + (size_t)blockIdx.y * n : p; }
+
 // 16-byte cells {low half | seq} {high half | seq} in device memory: how blocks of one launch hand each other a double without
 // a fence or a flag (k_lda_reduce_ll_mstep; the mailbox format of p2p.hip)
 __device__ __forceinline__ void cell_store(unsigned long long* c, double v, unsigned int seq)
@@ -202,6 +208,13 @@ __device__ unsigned long long g_ll_times[2][512];
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------------
+struct PinnedCtl {
+    LdaCtl* p = nullptr;
+    PinnedCtl() = default;
+    PinnedCtl(const PinnedCtl&) = delete; PinnedCtl& operator=(const PinnedCtl&) = delete;
+    ~PinnedCtl() { if (p) (void)hipHostFree(p); }
+};
+
 struct mmm_lda {
     mmm_ctx* ctx = nullptr;
     mmm_tuning_opts tune{};      // the caller's choices at create time (mmm_ctx_set_tuning)
@@ -253,9 +266,20 @@ struct mmm_lda {
     IldaDesc ids{};
     DevBuf<int> features;
     DevBuf<double> ilam[3], iEln[3], ibeta[3];      // model layout, ring like the V x K tables
+    // Batch handle (mmm_lda_create_batch, R > 1): the topic / document rings, the E-step and ll partials, stats, ll_hist and ctl hold R
+    // replicas back to back (replica-major; ll_hist at a stride of cap_hist); theta and phi are one buffer, formed for the selected
+    // replica on demand.  The host mirror (t, n_hist, ...) is the selected replica's; rep_t / rep_hist keep every replica's.
+    int R = 1, sel = 0;
+    std::vector<int> rep_t, rep_hist;
+    PinnedCtl pin;                      // fit_batch: in-stream snapshots of the R control blocks (two slots)
     LdaDev dev() const { return LdaDev{D, V, K, doc_ptr.p, tc.p, alpha, eta, tc_ell.p, (drows && !cnt16.p) ? cnt_dense.p : nullptr, 16 * SLs, cnt16.p}; }
     int cur() const { return t % 3; }
     Ring ring(DevBuf<double>* b) const { return Ring{{b[0].p, b[1].p, b[2].p}}; }
+    // the selected replica's slot s of a V x K ring / a K x D ring, its control block and ll history (R = 1: the arrays themselves)
+    double* tab(DevBuf<double>* b, int s) const { return b[s].p + (size_t)sel * V * K; }
+    double* doc(DevBuf<double>* b, int s) const { return b[s].p + (size_t)sel * K * D; }
+    LdaCtl* ctlp() const { return ctl.p + sel; }
+    double* hist() const { return ll_hist.p + (size_t)sel * cap_hist; }
 };
 
 namespace {
@@ -306,40 +330,41 @@ int residency_cap(mmm_lda* m, Kern kern, size_t lds, int* cap)
     return MMM_OK;
 }
 
-template <int KPV, int LV, bool LLV, int VT, bool SG>
+// RB: the batch builds, one grid.y row per replica (a handle is either a batch or not, so attr_e / attr_d name the builds it launches)
+template <int KPV, int LV, bool LLV, int VT, bool SG, bool RB>
 int go_estep3(mmm_lda* m, const EstepArgs& a)
 {
     mmm_ctx* ctx = m->ctx;
-    auto k = k_lda_estep<KPV, LV, LLV, VT, SG>;
+    auto k = k_lda_estep<KPV, LV, LLV, VT, SG, RB>;
     if (!m->attr_e[LLV]) { int rc = set_lds(ctx, k, m->lds_e); if (rc) return rc; m->attr_e[LLV] = true; }
-    hipLaunchKernelGGL(k, dim3(m->grid_e), dim3(m->waves_e * MMM_WAVE), m->lds_e, ctx->stream, a);
+    hipLaunchKernelGGL(k, dim3(m->grid_e, RB ? m->R : 1), dim3(m->waves_e * MMM_WAVE), m->lds_e, ctx->stream, a);
     return MMM_OK;
 }
 
-template <int KPV, int LV, bool LLV, int VT>
+template <int KPV, int LV, bool LLV, int VT, bool RB>
 int go_estep2(mmm_lda* m, const EstepArgs& a)
 {
-    if constexpr (LV == 16 && KPV <= 12) { if (m->single_step) return go_estep3<KPV, LV, LLV, VT, true>(m, a); }
-    return go_estep3<KPV, LV, LLV, VT, false>(m, a);
+    if constexpr (LV == 16 && KPV <= 12) { if (m->single_step) return go_estep3<KPV, LV, LLV, VT, true, RB>(m, a); }
+    return go_estep3<KPV, LV, LLV, VT, false, RB>(m, a);
 }
 
-template <int KPV, int LV, bool LLV>
+template <int KPV, int LV, bool LLV, bool RB = false>
 int go_estep(mmm_lda* m, const EstepArgs& a)
 {
     // the 96-term SNV vocabulary (data/brca-eu_snv_counts.tsv; every BASELINE config) gets compile-time strides
-    if constexpr (LV == 16 && (KPV == 8 || KPV == 10)) { if (m->V == 96) return go_estep2<KPV, LV, LLV, 96>(m, a); }
-    return go_estep2<KPV, LV, LLV, 0>(m, a);
+    if constexpr (LV == 16 && (KPV == 8 || KPV == 10)) { if (m->V == 96) return go_estep2<KPV, LV, LLV, 96, RB>(m, a); }
+    return go_estep2<KPV, LV, LLV, 0, RB>(m, a);
 }
 
-template <int KPV, int SLV>
+template <int KPV, int SLV, bool RB = false>
 int go_dense(mmm_lda* m, const EstepArgs& a)
 {
     if constexpr (KPV * SLV <= 64) {
         mmm_ctx* ctx = m->ctx;
         const bool c16 = m->cnt16.p != nullptr;
-        auto k = c16 ? k_lda_estep_dense<KPV, SLV, true> : k_lda_estep_dense<KPV, SLV, false>;
+        auto k = c16 ? k_lda_estep_dense<KPV, SLV, true, RB> : k_lda_estep_dense<KPV, SLV, false, RB>;
         if (!m->attr_d) { int rc = set_lds(ctx, k, m->lds_d); if (rc) return rc; m->attr_d = true; }
-        hipLaunchKernelGGL(k, dim3(m->grid_e), dim3(m->waves_e * MMM_WAVE), m->lds_d, ctx->stream, a, (const int*)m->cnt_dense.p, (const unsigned short*)m->cnt16.p);
+        hipLaunchKernelGGL(k, dim3(m->grid_e, RB ? m->R : 1), dim3(m->waves_e * MMM_WAVE), m->lds_d, ctx->stream, a, (const int*)m->cnt_dense.p, (const unsigned short*)m->cnt16.p);
         return MMM_OK;
     } else return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "LDA: no dense-row build for KP=%d SL=%d", KPV, SLV);
 }
@@ -347,6 +372,8 @@ int go_dense(mmm_lda* m, const EstepArgs& a)
 // term slots per lane of the dense-row build that covers V terms (0: none)
 int dense_slots(int V) { return V <= 32 ? 2 : (V <= 48 ? 3 : (V <= 96 ? 6 : (V <= 128 ? 8 : 0))); }
 
+// RB: a batched pass (split pipeline; the ll rides in the reduce launch, so a.do_ll = 0 and the wide path never comes here)
+template <bool RB = false>
 int launch_estep(mmm_lda* m, const EstepArgs& a)
 {
     mmm_ctx* ctx = m->ctx;
@@ -355,12 +382,23 @@ int launch_estep(mmm_lda* m, const EstepArgs& a)
         MMM_KP_SWITCH(m, {
             if constexpr (KPV >= 4 && KPV <= 16) {
                 switch (m->SL) {
-                    case 2: rc = go_dense<KPV, 2>(m, a); break;
-                    case 3: rc = go_dense<KPV, 3>(m, a); break;
-                    case 6: rc = go_dense<KPV, 6>(m, a); break;
-                    default: rc = go_dense<KPV, 8>(m, a); break;
+                    case 2: rc = go_dense<KPV, 2, RB>(m, a); break;
+                    case 3: rc = go_dense<KPV, 3, RB>(m, a); break;
+                    case 6: rc = go_dense<KPV, 6, RB>(m, a); break;
+                    default: rc = go_dense<KPV, 8, RB>(m, a); break;
                 }
             }
+        })
+        if (rc) return rc;
+        MMM_LAUNCH_CHECK(ctx);
+        return MMM_OK;
+    }
+    if constexpr (RB) {
+        if (m->wide || a.do_ll) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "LDA batch: no batched build of the wide path / the E-step ll");
+        MMM_KP_SWITCH(m, {
+            if (m->L == 16) { if constexpr (KPV <= 16) rc = go_estep<KPV, 16, false, true>(m, a); }
+            else if (m->L == 32) { if constexpr (KPV >= 16) rc = go_estep<KPV, 32, false, true>(m, a); }
+            else { if constexpr (KPV == 32) rc = go_estep<KPV, 64, false, true>(m, a); }
         })
         if (rc) return rc;
         MMM_LAUNCH_CHECK(ctx);
@@ -450,7 +488,7 @@ int sync_ctl(mmm_lda* m)
     if (!m->inflight) return MMM_OK;
     mmm_ctx* ctx = m->ctx;
     LdaCtl h;
-    MMM_HIP(ctx, hipMemcpyAsync(&h, m->ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipMemcpyAsync(&h, m->ctlp(), sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     { int rc = mmm_p2p_check(ctx); if (rc) return rc; }
     if (h.wait_timeout) return mmm_fail(ctx, MMM_ERR_HIP, "LDA: a block of the merged reduce + M-step launch gave up waiting for its neighbours");
@@ -469,8 +507,8 @@ int materialise_phi(mmm_lda* m)
     if (rc) return rc;
     if (m->phi_valid) return MMM_OK;
     const int c = m->cur(), p = (m->t + 2) % 3;
-    const double* table = m->phi_from_prev ? (m->phi_table_beta ? m->beta[p].p : m->expElnbeta[p].p) : m->expElnbeta[c].p;
-    if ((rc = launch_phi(m, m->Elntheta[c].p, table))) return rc;
+    const double* table = m->phi_from_prev ? (m->phi_table_beta ? m->tab(m->beta, p) : m->tab(m->expElnbeta, p)) : m->tab(m->expElnbeta, c);
+    if ((rc = launch_phi(m, m->doc(m->Elntheta, c), table))) return rc;
     m->phi_valid = true;
     return MMM_OK;
 }
@@ -482,8 +520,11 @@ int ensure_hist(mmm_lda* m, int extra)
     if (rc) return rc;
     const int cap = std::max(2 * m->cap_hist, m->n_hist + extra + 66);
     DevBuf<double> nb;
-    MMM_HIP(m->ctx, nb.alloc(cap));
-    if (m->n_hist) MMM_HIP(m->ctx, hipMemcpyAsync(nb.p, m->ll_hist.p, sizeof(double) * m->n_hist, hipMemcpyDeviceToDevice, m->ctx->stream));
+    MMM_HIP(m->ctx, nb.alloc((size_t)cap * m->R));
+    if (m->R > 1 && m->cap_hist)      // every replica's history (fit_batch keeps the replicas' lengths equal when it grows them)
+        MMM_HIP(m->ctx, hipMemcpy2DAsync(nb.p, sizeof(double) * cap, m->ll_hist.p, sizeof(double) * m->cap_hist, sizeof(double) * m->cap_hist, m->R,
+                                         hipMemcpyDeviceToDevice, m->ctx->stream));
+    else if (m->n_hist) MMM_HIP(m->ctx, hipMemcpyAsync(nb.p, m->ll_hist.p, sizeof(double) * m->n_hist, hipMemcpyDeviceToDevice, m->ctx->stream));
     MMM_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
     m->ll_hist.swap(nb);
     m->cap_hist = cap;
@@ -499,14 +540,14 @@ int flush_ll(mmm_lda* m, double* also_dev)
     mmm_ctx* ctx = m->ctx;
     const int c = m->cur();
     if ((rc = ensure_hist(m, 1))) return rc;
-    if ((rc = launch_loglik(m, m->gamma[c].p, m->beta[c].p, m->theta.p, 1))) return rc;
+    if ((rc = launch_loglik(m, m->doc(m->gamma, c), m->tab(m->beta, c), m->theta.p, 1))) return rc;
     m->theta_valid = true;
     double* num = m->scratch.p + (size_t)m->V * m->K;
     hipLaunchKernelGGL(k_sum_columns, dim3(1), dim3(64), 0, ctx->stream, m->llpart.p, m->grid_s, 1, num);
     MMM_LAUNCH_CHECK(ctx);
     if ((rc = mmm_allreduce_sum(ctx, num, 1))) return rc;
     const bool push = m->ll_pending;
-    hipLaunchKernelGGL(k_ll_push, dim3(1), dim3(1), 0, ctx->stream, m->ctl.p, num, m->Nglobal, push ? m->ll_hist.p : nullptr, also_dev);
+    hipLaunchKernelGGL(k_ll_push, dim3(1), dim3(1), 0, ctx->stream, m->ctlp(), num, m->Nglobal, push ? m->hist() : nullptr, also_dev);
     MMM_LAUNCH_CHECK(ctx);
     if (push) { m->n_hist++; m->ll_pending = false; }
     return MMM_OK;
@@ -549,7 +590,7 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
         // Where the ll of pass t-1 is evaluated: in extra blocks of the reduce launch (the reduction occupies 60 CUs for ~6 us,
         // the ll sweep fits beside it and the E-step kernel sheds 43 % of its chunk-loop instructions and half its table
         // reads).
-        ReduceArgs r{m->partial.p, m->llpart.p, m->grid_e, VK, m->stats[t & 1].p, m->ctl.p, t, m->Nglobal, tol, m->ll_hist.p, do_ll, conv_base, 1};
+        ReduceArgs r{m->partial.p, m->llpart.p, m->grid_e, VK, m->stats[t & 1].p, m->ctl.p, t, 0, m->Nglobal, tol, m->ll_hist.p, do_ll, conv_base, 1};
         r.p2p = 0; r.p2p_seq = 0;
         const bool fold = !mmm_off(m->tune, MMM_OFF_P2P_FOLDED);
         const int Vp = (m->V + 15) & ~15;
@@ -687,6 +728,71 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
     return MMM_OK;
 }
 
+// n_iter passes of a batch handle (R > 1): the split pipeline of fused_passes (MMM_OFF_LDA_MERGED, one GPU) with the replica on grid.y of
+// every launch -- the E-step build, k_lda_reduce[_ll] and k_lda_mstep of a single handle of this shape, over the same geometry (grid_e,
+// reduce and ll blocks come from D alone), hence each replica's bits are those of its single fit.  No merged launch: its blocks wait for
+// each other, which needs them all resident, and R replicas on grid.y break that bound.  A replica whose stopping rule has fired
+// (its own ctl) turns every later launch into a no-op for itself.
+int batch_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
+{
+    mmm_ctx* ctx = m->ctx;
+    int rc;
+    const int R = m->R;
+    if (!m->gnext_valid) {
+        // update_γ! for the first pass from the resident phi (LDA.jl:82-90): the constructor's 1/K, the same for every replica (the calls
+        // that could change it are refused on batch handles)
+        const size_t KD = (size_t)m->K * m->D;
+        for (int r = 0; r < R; ++r)
+            hipLaunchKernelGGL(k_lda_gamma_from_phi, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->gamma[(m->t + 1) % 3].p + r * KD, (double*)nullptr);
+        MMM_LAUNCH_CHECK(ctx);
+        m->gnext_valid = true;
+    }
+    const int VK = m->V * m->K;
+    const size_t lds_red = sizeof(double) * ((size_t)m->KP * m->V + 64 * (size_t)m->KP + MMM_LOGTAB_N);
+    const int docs_per_ll_block = 16 * (MMM_WAVE / (m->KP <= 15 ? 16 : (m->KP <= 31 ? 32 : 64)));
+    const int blocks_ll = (m->D + docs_per_ll_block - 1) / docs_per_ll_block;
+    const int nred = (VK + 15) / 16;
+    for (int it = 0; it < n_iter; ++it) {
+        const int t = m->t + 1;
+        const int do_ll = (m->ll_pending || it > 0) ? 1 : 0;
+        ReduceArgs r{m->partial.p, m->llpart.p, m->grid_e, VK, m->stats[t & 1].p, m->ctl.p, t, m->cap_hist, m->Nglobal, tol, m->ll_hist.p, do_ll, conv_base, 1};
+        r.p2p = 0; r.p2p_seq = 0;
+        r.llpart2 = m->llpart2.p; r.ll_in_k2 = 1;
+        r.ll_cells = nullptr; r.ll_seq = 0;
+        r.n_ll = do_ll ? std::max(1, std::min(blocks_ll, 512)) : 0;
+        LdaDev edev = m->dev();
+        if (mmm_off(m->tune, MMM_OFF_LDA_PADDED_ROWS)) { edev.ell = nullptr; edev.dense = nullptr; edev.dense16 = nullptr; }
+        EstepArgs a{edev, m->ctl.p, m->ring(m->gamma), m->ring(m->Elntheta), m->ring(m->expElnbeta), m->ring(m->beta),
+                    m->partial.p, m->llpart.p, 0, t, m->V};
+        {
+            ProfSpan span(ctx);
+            rc = launch_estep<true>(m, a);
+        }
+        if (rc) return rc;
+        ProfSpan tail_span(ctx, 1);
+        if (r.n_ll > 0) {
+            MMM_KP_SWITCH(m, {
+                auto k = k_lda_reduce_ll<KPV, true>;
+                if (!m->attr_m) { if ((rc = set_lds(ctx, k, lds_red))) return rc; m->attr_m = true; }
+                hipLaunchKernelGGL(k, dim3(nred + r.n_ll, R), dim3(16, 64), lds_red, ctx->stream, r, m->dev(), m->gamma[(t + 2) % 3].p, m->beta[(t + 2) % 3].p,
+                                   m->llpart2.p, nred);
+            })
+        } else hipLaunchKernelGGL(k_lda_reduce<true>, dim3(nred, R), dim3(16, 64), 0, ctx->stream, r);
+        MMM_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL((k_lda_mstep<false, true>), dim3(m->K + 1, R), dim3(128), 0, ctx->stream, r, m->V, m->eta, m->ring(m->lambda),
+                           m->ring(m->Elnbeta), m->ring(m->expElnbeta), m->ring(m->beta));
+        MMM_LAUNCH_CHECK(ctx);
+        if (do_ll) m->n_hist++;
+        m->t = t;
+        m->ll_pending = true;
+    }
+    if (n_iter > 0) {
+        m->inflight = true; m->lag_ll = true; m->phi_table_beta = false;
+        m->phi_valid = false; m->phi_from_prev = true; m->gnext_valid = true; m->theta_valid = false;
+    }
+    return MMM_OK;
+}
+
 // n_iter frozen-topic passes: update_γ!, (unsmoothed_)update_ϕ!, update_θ!, ll (LDA.jl:241-247 / :274-279).  The topic state
 // must be replicated in the three ring slots (mmm_lda_infer does that once).
 int frozen_passes(mmm_lda* m, int n_iter, int unsmoothed, double tol, int conv_base)
@@ -711,7 +817,7 @@ int frozen_passes(mmm_lda* m, int n_iter, int unsmoothed, double tol, int conv_b
                     m->partial.p, m->llpart.p, 1, t, m->V};
         { ProfSpan span(ctx); rc = launch_estep(m, a); }
         if (rc) return rc;
-        ReduceArgs r{m->partial.p, m->llpart.p, m->grid_e, VK, m->stats[t & 1].p, m->ctl.p, t, m->Nglobal, tol, m->ll_hist.p, 1, conv_base, 1};
+        ReduceArgs r{m->partial.p, m->llpart.p, m->grid_e, VK, m->stats[t & 1].p, m->ctl.p, t, 0, m->Nglobal, tol, m->ll_hist.p, 1, conv_base, 1};
         if (!comm) hipLaunchKernelGGL(k_lda_infer_tail, dim3(1), dim3(64), 0, ctx->stream, r, 3);
         else {
             hipLaunchKernelGGL(k_lda_infer_tail, dim3(1), dim3(64), 0, ctx->stream, r, 1);
@@ -785,13 +891,21 @@ extern "C" int mmm_diag_red_stamps(unsigned long long out[32])
 }
 #endif
 
+// entry points that act on one model's state step by step: a batch handle (R > 1) only fits all its replicas together
+#define MMM_NOT_ON_BATCH(m, what)                                                                                              \
+    do {                                                                                                                       \
+        if ((m)->R > 1)                                                                                                        \
+            return mmm_fail((m)->ctx, MMM_ERR_UNSUPPORTED, "%s: not available on a batch handle (%d replicas): fit them with mmm_lda_fit_batch, " \
+                            "or use a single handle (mmm_lda_create)", what, (m)->R);                                         \
+    } while (0)
+
 extern "C" {
 
 constexpr int kMinWavesSingle = 4;      // single-step build: fewest waves per block the library picks by itself (shard sizes: profiles/r05_lda_small_shards.txt)
 
 static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, double eta, const int64_t* doc_ptr, const int32_t* term,
                            const int32_t* count, const double* lambda0, int I, const int* J, const double* eta_i, const int32_t* features,
-                           mmm_lda** out)
+                           mmm_lda** out, int R = 1)
 {
     if (!ctx) return MMM_ERR_ARG;
     MMM_CHECK(ctx, out && doc_ptr && lambda0, "mmm_lda_create: NULL argument");
@@ -864,16 +978,24 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     // spills (10k x 96-term documents, K = 32: 264 us per iteration against 189).  lda_build = MMM_BUILD_WIDE forces it, MMM_BUILD_SPARSE /
     // _DENSE avoid it where the LDS kernels can run (tests, A/B).
     const bool wide = lds_for(waves) > 160 * 1024 || KP > 32 || (ctx->tune.lda_build == MMM_BUILD_WIDE) || (ctx->tune.lda_build == MMM_BUILD_AUTO && KP >= 32);
+    if (R > 1 && wide) {
+        const char* why = ctx->tune.lda_build == MMM_BUILD_WIDE ? "lda_build = MMM_BUILD_WIDE takes the wide path (tables through L2)"
+                        : KP > 32 ? "K > 32 topics take the wide path (no LDS build)"
+                        : ctx->tune.lda_build == MMM_BUILD_AUTO && KP >= 32 ? "K >= 25 topics take the wide path under MMM_BUILD_AUTO"
+                        : "the K x V tables and one slab exceed LDS (wide path)";
+        return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_create_batch: K=%d V=%d: %s, which has no batched build -- fit such shapes on single handles", K, V, why);
+    }
 
     MMM_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<mmm_lda> guard(new mmm_lda());      // every early return below (MMM_HIP, ...) destroys the model and its buffers
     mmm_lda* m = guard.get();
     m->tune = ctx->tune;
     m->ctx = ctx; m->D = D; m->V = V; m->K = K; m->KP = KP; m->L = L; m->nnz = nnz; m->alpha = alpha; m->eta = eta;
+    m->R = R; m->rep_t.assign((size_t)R, 0); m->rep_hist.assign((size_t)R, 0);
     m->waves_e = waves; m->lds_e = wide ? 0 : lds_for(waves); m->lds_tab = tabB; m->wide = wide;
     m->dense = dense && !wide; m->SL = SL; m->drows = (dense || drows) && !wide;
     if (!wide && ctx->tune.waves_per_block > 0) { const int w = ctx->tune.waves_per_block; if (w >= 1 && w <= (small ? kMaxWavesE : 8) && lds_for(w) <= 160 * 1024) { m->waves_e = w; m->lds_e = lds_for(w); } }
-    const size_t VK = (size_t)V * K, KD = (size_t)K * D;
+    const size_t VK = (size_t)V * K, KD = (size_t)K * D, Rs = (size_t)R;
     const int docs_per_block = m->waves_e * G;
     const int blocks_per_cu = wide ? 8 : std::max(1, std::min<int>((small ? 12 : 8) / m->waves_e, (int)((160 * 1024) / m->lds_e)));
     m->single_step = !wide && small && (int64_t)m->waves_e * G * ncu * blocks_per_cu >= D;      // the grid covers every document at once
@@ -888,11 +1010,12 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     const int grid_max = std::max(m->grid_e, m->grid_s);
 #define A(buf, n) do { hipError_t e_ = m->buf.alloc(n); if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(" #buf "): %s", hipGetErrorString(e_)); return rc; } } while (0)
     A(doc_ptr, (size_t)D + 1); A(tc, (size_t)nnz);
-    for (int i = 0; i < 3; ++i) { A(lambda[i], VK); A(Elnbeta[i], VK); A(expElnbeta[i], VK); A(beta[i], VK); A(gamma[i], KD); A(Elntheta[i], KD); }
+    for (int i = 0; i < 3; ++i) { A(lambda[i], Rs * VK); A(Elnbeta[i], Rs * VK); A(expElnbeta[i], Rs * VK); A(beta[i], Rs * VK); A(gamma[i], Rs * KD); A(Elntheta[i], Rs * KD); }
     A(theta, KD); A(phi, (size_t)K * nnz);
     const size_t VKp = (size_t)((V + 15) & ~15) * K;       // rows padded to 16 (k_lda_reduce_ll_mstep)
-    A(partial, wide ? 1 : (size_t)m->grid_e * VKp); A(stats[0], VKp + 16); A(stats[1], VKp + 16); A(scratch, VK + 16); A(llpart, (size_t)grid_max); A(llpart2, 1024); A(elbopart, (size_t)m->grid_s * 5 + 8);
-    A(ctl, 1); A(cells, 2 * 1024);
+    A(partial, wide ? 1 : Rs * m->grid_e * VKp); A(stats[0], Rs * (VKp + 16)); A(stats[1], Rs * (VKp + 16)); A(scratch, VK + 16); A(llpart, Rs * grid_max);
+    A(llpart2, Rs * 1024); A(elbopart, (size_t)m->grid_s * 5 + 8 * Rs);
+    A(ctl, Rs); A(cells, 2 * 1024);
     if (m->single_step && !ilda) A(aexp_next, KD);
     if (ilda) {
         A(fcells, (size_t)2 * 512 * 16);
@@ -960,7 +1083,7 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
             MMM_HIP(ctx, hipMemcpyAsync(m->tc_ell.p, ell.data(), sizeof(int2) * ell.size(), hipMemcpyHostToDevice, st));
         }
     }
-    if (!ilda) MMM_HIP(ctx, hipMemcpyAsync(m->lambda[0].p, lambda0, sizeof(double) * VK, hipMemcpyHostToDevice, st));
+    if (!ilda) MMM_HIP(ctx, hipMemcpyAsync(m->lambda[0].p, lambda0, sizeof(double) * VK * Rs, hipMemcpyHostToDevice, st));
     else {
         m->ilda = true;
         IldaDesc& ds = m->ids;
@@ -971,19 +1094,23 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
         MMM_HIP(ctx, hipMemcpyAsync(m->ilam[0].p, lambda0, sizeof(double) * (size_t)SJ * K, hipMemcpyHostToDevice, st));
         for (int i = 0; i < 3; ++i) MMM_HIP(ctx, hipMemsetAsync(m->lambda[i].p, 0, sizeof(double) * VK, st));      // unused for ILDA
     }
-    MMM_HIP(ctx, hipMemsetAsync(m->ctl.p, 0, sizeof(LdaCtl), st));
+    MMM_HIP(ctx, hipMemsetAsync(m->ctl.p, 0, sizeof(LdaCtl) * Rs, st));
     MMM_HIP(ctx, hipMemsetAsync(m->cells.p, 0, sizeof(unsigned long long) * 2 * 1024, st));
     if (ilda) MMM_HIP(ctx, hipMemsetAsync(m->fcells.p, 0, sizeof(unsigned long long) * 2 * 512 * 16, st));
-    if (!wide) MMM_HIP(ctx, hipMemsetAsync(m->partial.p, 0, sizeof(double) * (size_t)m->grid_e * VKp, st));      // pad entries are never written
+    if (!wide) MMM_HIP(ctx, hipMemsetAsync(m->partial.p, 0, sizeof(double) * Rs * m->grid_e * VKp, st));      // pad entries are never written
     if (KD) MMM_HIP(ctx, hipMemsetAsync(m->theta.p, 0, sizeof(double) * KD, st));
     MMM_HIP(ctx, hipStreamSynchronize(st));   // tc (host vector) must outlive the copy
     // constructor state (LDA.jl:36-49): Elnbeta from lambda0; gamma = 1 -> Elntheta; phi = 1/K
-    if (!ilda) hipLaunchKernelGGL(k_lda_topic, dim3(K), dim3(256), 0, st, V, eta, (const double*)nullptr, m->lambda[0].p, m->Elnbeta[0].p, m->expElnbeta[0].p, m->beta[0].p, 0);
-    else hipLaunchKernelGGL(k_ilda_mstep, dim3(K), dim3(64 * m->ids.I), 0, st, m->ids, 1, (const double*)nullptr, m->ilam[0].p, m->iEln[0].p, m->ibeta[0].p,
-                            m->Elnbeta[0].p, m->expElnbeta[0].p, m->beta[0].p, (const int*)nullptr, 0, ReduceArgs{}, 0);      // ILDA.jl:36-40 (+ tables)
+    for (size_t r = 0; r < Rs && !ilda; ++r)
+        hipLaunchKernelGGL(k_lda_topic, dim3(K), dim3(256), 0, st, V, eta, (const double*)nullptr, m->lambda[0].p + r * VK, m->Elnbeta[0].p + r * VK, m->expElnbeta[0].p + r * VK,
+                           m->beta[0].p + r * VK, 0);
+    if (ilda)
+        hipLaunchKernelGGL(k_ilda_mstep, dim3(K), dim3(64 * m->ids.I), 0, st, m->ids, 1, (const double*)nullptr, m->ilam[0].p, m->iEln[0].p, m->ibeta[0].p,
+                           m->Elnbeta[0].p, m->expElnbeta[0].p, m->beta[0].p, (const int*)nullptr, 0, ReduceArgs{}, 0);      // ILDA.jl:36-40 (+ tables)
     if (KD) {
-        hipLaunchKernelGGL(k_fill, dim3((unsigned)((KD + 255) / 256)), dim3(256), 0, st, m->gamma[0].p, KD, 1.0);
-        hipLaunchKernelGGL(m->K > 64 ? k_lda_Elntheta_big : k_lda_Elntheta, dim3(m->grid_s), dim3(kBlock), 0, st, m->dev(), m->gamma[0].p, m->Elntheta[0].p);
+        hipLaunchKernelGGL(k_fill, dim3((unsigned)((Rs * KD + 255) / 256)), dim3(256), 0, st, m->gamma[0].p, Rs * KD, 1.0);
+        for (size_t r = 0; r < Rs; ++r)
+            hipLaunchKernelGGL(m->K > 64 ? k_lda_Elntheta_big : k_lda_Elntheta, dim3(m->grid_s), dim3(kBlock), 0, st, m->dev(), m->gamma[0].p + r * KD, m->Elntheta[0].p + r * KD);
     }
     if (nnz) hipLaunchKernelGGL(k_fill, dim3((unsigned)(((size_t)K * nnz + 255) / 256)), dim3(256), 0, st, m->phi.p, (size_t)K * nnz, 1.0 / K);
     MMM_HIP(ctx, hipMemsetAsync(m->scratch.p, 0, sizeof(double) * (VK + 16), st));
@@ -1038,11 +1165,11 @@ static int lda_field(mmm_lda* m, int field, double** p, size_t* n)
     const size_t VK = (size_t)m->V * m->K, KD = (size_t)m->K * m->D;
     const int c = m->cur();
     switch (field) {
-        case MMM_LDA_LAMBDA: *p = m->lambda[c].p; *n = VK; break;
-        case MMM_LDA_ELNBETA: *p = m->Elnbeta[c].p; *n = VK; break;
-        case MMM_LDA_BETA: *p = m->beta[c].p; *n = VK; break;
-        case MMM_LDA_GAMMA: *p = m->gamma[c].p; *n = KD; break;
-        case MMM_LDA_ELNTHETA: *p = m->Elntheta[c].p; *n = KD; break;
+        case MMM_LDA_LAMBDA: *p = m->tab(m->lambda, c); *n = VK; break;
+        case MMM_LDA_ELNBETA: *p = m->tab(m->Elnbeta, c); *n = VK; break;
+        case MMM_LDA_BETA: *p = m->tab(m->beta, c); *n = VK; break;
+        case MMM_LDA_GAMMA: *p = m->doc(m->gamma, c); *n = KD; break;
+        case MMM_LDA_ELNTHETA: *p = m->doc(m->Elntheta, c); *n = KD; break;
         case MMM_LDA_THETA: *p = m->theta.p; *n = KD; break;
         case MMM_LDA_PHI: *p = m->phi.p; *n = (size_t)m->K * m->nnz; break;
         case MMM_ILDA_LAMBDA: case MMM_ILDA_ELNBETA: case MMM_ILDA_BETA:
@@ -1065,7 +1192,7 @@ int mmm_lda_get(mmm_lda* m, int field, double* host, size_t n)
     MMM_CHECK(ctx, host && n == cnt, "mmm_lda_get(field %d): expected %zu doubles, got %zu", field, cnt, n);
     if (field == MMM_LDA_PHI && (rc = materialise_phi(m))) return rc;
     if (field == MMM_LDA_THETA && !m->theta_valid && m->t > 0) {       // fit! leaves theta = gamma/sum (LDA.jl:207)
-        if ((rc = launch_loglik(m, m->gamma[m->cur()].p, nullptr, m->theta.p, 0))) return rc;
+        if ((rc = launch_loglik(m, m->doc(m->gamma, m->cur()), nullptr, m->theta.p, 0))) return rc;
         m->theta_valid = true;
     }
     if (n) MMM_HIP(ctx, hipMemcpyAsync(host, p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1076,6 +1203,7 @@ int mmm_lda_get(mmm_lda* m, int field, double* host, size_t n)
 int mmm_lda_set(mmm_lda* m, int field, const double* host, size_t n)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_set");
     mmm_ctx* ctx = m->ctx;
     int rc = prepare_call(m);
     if (rc) return rc;
@@ -1105,6 +1233,7 @@ int mmm_lda_set(mmm_lda* m, int field, const double* host, size_t n)
 int mmm_lda_set_hyper(mmm_lda* m, double alpha, const double* eta, int n_eta)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_set_hyper");
     mmm_ctx* ctx = m->ctx;
     int rc = prepare_call(m);
     if (rc) return rc;
@@ -1123,6 +1252,7 @@ int mmm_lda_set_hyper(mmm_lda* m, double alpha, const double* eta, int n_eta)
 int mmm_lda_update_gamma(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_gamma");
     int rc = prepare_call(m);
     if (rc || (rc = materialise_phi(m)) || (rc = flush_ll(m, nullptr))) return rc;
     const int c = m->cur();
@@ -1135,6 +1265,7 @@ int mmm_lda_update_gamma(mmm_lda* m)
 int mmm_lda_update_phi(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_phi");
     int rc = prepare_call(m);
     if (rc || (rc = flush_ll(m, nullptr))) return rc;
     const int c = m->cur();
@@ -1146,6 +1277,7 @@ int mmm_lda_update_phi(mmm_lda* m)
 int mmm_lda_update_lambda(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_lambda");
     mmm_ctx* ctx = m->ctx;
     int rc = prepare_call(m);
     if (rc || (rc = materialise_phi(m)) || (rc = flush_ll(m, nullptr))) return rc;
@@ -1159,6 +1291,7 @@ int mmm_lda_update_lambda(mmm_lda* m)
 int mmm_lda_update_Elntheta(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_Elntheta");
     int rc = prepare_call(m);
     if (rc || (rc = materialise_phi(m)) || (rc = flush_ll(m, nullptr))) return rc;
     const int c = m->cur();
@@ -1171,6 +1304,7 @@ int mmm_lda_update_Elntheta(mmm_lda* m)
 int mmm_lda_update_Elnbeta(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_Elnbeta");
     int rc = prepare_call(m);
     if (rc || (rc = materialise_phi(m)) || (rc = flush_ll(m, nullptr))) return rc;
     m->gnext_valid = false; m->phi_from_prev = false;
@@ -1180,6 +1314,7 @@ int mmm_lda_update_Elnbeta(mmm_lda* m)
 int mmm_lda_update_beta(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_beta");
     int rc = prepare_call(m);
     if (rc) return rc;
     const int c = m->cur();
@@ -1196,6 +1331,7 @@ int mmm_lda_update_beta(mmm_lda* m)
 int mmm_lda_update_theta(mmm_lda* m)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_update_theta");
     int rc = prepare_call(m);
     if (rc) return rc;
     if ((rc = launch_loglik(m, m->gamma[m->cur()].p, nullptr, m->theta.p, 0))) return rc;
@@ -1206,6 +1342,7 @@ int mmm_lda_update_theta(mmm_lda* m)
 int mmm_lda_loglik(mmm_lda* m, double* ll)
 {
     if (!m || !ll) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_loglik");
     mmm_ctx* ctx = m->ctx;
     int rc = prepare_call(m);
     if (rc) return rc;
@@ -1221,6 +1358,7 @@ int mmm_lda_loglik(mmm_lda* m, double* ll)
 int mmm_lda_iterate(mmm_lda* m, int n_iter)
 {
     if (!m) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_iterate");
     mmm_ctx* ctx = m->ctx;
     if (int rc = mmm_ctx_usable(ctx, "mmm_lda_iterate")) return rc;
     MMM_HIP(ctx, hipSetDevice(ctx->device));
@@ -1259,7 +1397,7 @@ int mmm_lda_ll_history(mmm_lda* m, double* ll, int max_n, int* n)
     int rc = prepare_call(m);
     if (rc || (rc = flush_ll(m, nullptr))) return rc;
     const int cnt = std::min(max_n, m->n_hist);
-    if (cnt > 0 && ll) MMM_HIP(ctx, hipMemcpyAsync(ll, m->ll_hist.p + (m->n_hist - cnt), sizeof(double) * cnt, hipMemcpyDeviceToHost, ctx->stream));
+    if (cnt > 0 && ll) MMM_HIP(ctx, hipMemcpyAsync(ll, m->hist() + (m->n_hist - cnt), sizeof(double) * cnt, hipMemcpyDeviceToHost, ctx->stream));
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // (the flush ends in the ranks' exchange: a peer that never came -- e.g. a caller that reads the history on one rank only -- must be an
     // error here, not a silently wrong last row)
@@ -1275,7 +1413,7 @@ int mmm_lda_events(mmm_lda* m, int64_t out[4])
     int rc = prepare_call(m);
     if (rc || (rc = flush_ll(m, nullptr))) return rc;
     std::vector<double> ll((size_t)std::max(m->n_hist, 0));
-    if (!ll.empty()) MMM_HIP(ctx, hipMemcpyAsync(ll.data(), m->ll_hist.p, sizeof(double) * ll.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (!ll.empty()) MMM_HIP(ctx, hipMemcpyAsync(ll.data(), m->hist(), sizeof(double) * ll.size(), hipMemcpyDeviceToHost, ctx->stream));
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = mmm_p2p_check(ctx))) return rc;
     out[0] = out[1] = out[2] = out[3] = 0;
@@ -1283,24 +1421,40 @@ int mmm_lda_events(mmm_lda* m, int64_t out[4])
     return MMM_OK;
 }
 
+// calculate_elbo's sums over the documents and topics of the selected replica into acc[0..6] (phi must be materialised)
+static int lda_elbo_enqueue(mmm_lda* m, double* acc)
+{
+    mmm_ctx* ctx = m->ctx;
+    const int c = m->cur();
+    hipLaunchKernelGGL(m->K > 64 ? k_lda_elbo_docs_big : k_lda_elbo_docs, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->doc(m->gamma, c), m->doc(m->Elntheta, c), m->tab(m->Elnbeta, c), m->elbopart.p);
+    hipLaunchKernelGGL(k_sum_columns, dim3(5), dim3(64), 0, ctx->stream, m->elbopart.p, m->grid_s, 5, acc);
+    if (m->ilda) hipLaunchKernelGGL(k_ilda_elbo_topics, dim3(1), dim3(256), 0, ctx->stream, m->ids, m->ilam[c].p, m->iEln[c].p, acc + 5);
+    else hipLaunchKernelGGL(k_lda_elbo_topics, dim3(1), dim3(256), 0, ctx->stream, m->V, m->K, m->tab(m->lambda, c), m->tab(m->Elnbeta, c), acc + 5);
+    MMM_LAUNCH_CHECK(ctx);
+    return MMM_OK;
+}
+
+static void lda_elbo_finish(const mmm_lda* m, const double h[7], double* elbo, double terms[7]);
+
 int mmm_lda_elbo(mmm_lda* m, double* elbo, double terms[7])
 {
     if (!m || !elbo) return MMM_ERR_ARG;
     mmm_ctx* ctx = m->ctx;
     int rc = prepare_call(m);
     if (rc || (rc = materialise_phi(m))) return rc;
-    const int c = m->cur();
     double* acc = m->elbopart.p + (size_t)m->grid_s * 5;      // [0..4] doc sums, [5..6] topic sums
-    hipLaunchKernelGGL(m->K > 64 ? k_lda_elbo_docs_big : k_lda_elbo_docs, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->gamma[c].p, m->Elntheta[c].p, m->Elnbeta[c].p, m->elbopart.p);
-    hipLaunchKernelGGL(k_sum_columns, dim3(5), dim3(64), 0, ctx->stream, m->elbopart.p, m->grid_s, 5, acc);
-    if (m->ilda) hipLaunchKernelGGL(k_ilda_elbo_topics, dim3(1), dim3(256), 0, ctx->stream, m->ids, m->ilam[c].p, m->iEln[c].p, acc + 5);
-    else hipLaunchKernelGGL(k_lda_elbo_topics, dim3(1), dim3(256), 0, ctx->stream, m->V, m->K, m->lambda[c].p, m->Elnbeta[c].p, acc + 5);
-    MMM_LAUNCH_CHECK(ctx);
+    if ((rc = lda_elbo_enqueue(m, acc))) return rc;
     if ((rc = mmm_allreduce_sum(ctx, acc, 5))) return rc;
     double h[7];
     MMM_HIP(ctx, hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = mmm_p2p_check(ctx))) return rc;
+    lda_elbo_finish(m, h, elbo, terms);
+    return MMM_OK;
+}
+
+static void lda_elbo_finish(const mmm_lda* m, const double h[7], double* elbo, double terms[7])
+{
     const double K = m->K, V = m->V, al = m->alpha, et = m->eta;
     double t[7];
     t[0] = K * (lgamma(V * et) - V * lgamma(et)) + (et - 1.0) * h[5];            // LDA.jl:114-118
@@ -1312,12 +1466,12 @@ int mmm_lda_elbo(mmm_lda* m, double* elbo, double terms[7])
     t[2] = h[1]; t[3] = h[2]; t[4] = h[6]; t[5] = h[4]; t[6] = h[3];
     if (terms) memcpy(terms, t, sizeof t);
     *elbo = t[0] + t[1] + t[2] + t[3] - t[4] - t[5] - t[6];
-    return MMM_OK;
 }
 
 int mmm_lda_fit(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged, double* elbo)
 {
     if (!m || !n_iter || !converged) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_fit");
     mmm_ctx* ctx = m->ctx;
     MMM_CHECK(ctx, maxiter >= 1, "mmm_lda_fit: maxiter < 1");
     int rc = prepare_call(m);
@@ -1352,6 +1506,7 @@ int mmm_lda_fit(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_ite
 int mmm_lda_infer(mmm_lda* m, int unsmoothed, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged)
 {
     if (!m || !n_iter || !converged) return MMM_ERR_ARG;
+    MMM_NOT_ON_BATCH(m, "mmm_lda_infer");
     mmm_ctx* ctx = m->ctx;
     MMM_CHECK(ctx, maxiter >= 1, "mmm_lda_infer: maxiter < 1");
     int rc = prepare_call(m);
@@ -1386,6 +1541,127 @@ int mmm_lda_infer(mmm_lda* m, int unsmoothed, int maxiter, double tol, double* l
     *n_iter = n;
     if (ll_hist && n > 0) MMM_HIP(ctx, hipMemcpyAsync(ll_hist, m->ll_hist.p + base, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MMM_OK;
+}
+
+// ---- restart batches: R models over one resident corpus (see include/mmmusig.h) ------------------------------------------
+int mmm_lda_create_batch(mmm_ctx* ctx, int R, int D, int V, int K, double alpha, double eta, const int64_t* doc_ptr, const int32_t* term,
+                         const int32_t* count, const double* lambda0, mmm_lda** out)
+{
+    if (!ctx) return MMM_ERR_ARG;
+    MMM_CHECK(ctx, R >= 1, "mmm_lda_create_batch: R=%d replicas (at least 1)", R);
+    if (R == 1) return mmm_lda_create(ctx, D, V, K, alpha, eta, doc_ptr, term, count, lambda0, out);      // the ordinary handle
+    if (ctx->nranks > 1 || ctx->comm)
+        return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_create_batch: the context has a communicator (%d ranks): a batch holds the whole corpus -- "
+                        "deal the restarts over the ranks on the host, each rank on a context without one", ctx->nranks);
+    return lda_create_impl(ctx, D, V, K, alpha, eta, doc_ptr, term, count, lambda0, 0, nullptr, nullptr, nullptr, out, R);
+}
+
+int mmm_lda_replicas(const mmm_lda* m) { return m ? m->R : MMM_ERR_ARG; }
+
+// make replica r the one the per-model entry points act on (its host mirror; theta and an implied phi are formed again on demand)
+static void lda_load_replica(mmm_lda* m, int r)
+{
+    m->sel = r; m->t = m->rep_t[(size_t)r]; m->n_hist = m->rep_hist[(size_t)r];
+    if (m->phi_from_prev) m->phi_valid = false;      // (a fresh batch's phi is the constructor's 1/K, the same for every replica)
+    m->theta_valid = false;
+}
+
+int mmm_lda_select(mmm_lda* m, int r)
+{
+    if (!m) return MMM_ERR_ARG;
+    MMM_CHECK(m->ctx, r >= 0 && r < m->R, "mmm_lda_select: replica %d of %d", r, m->R);
+    if (m->R == 1) return MMM_OK;
+    int rc = prepare_call(m);
+    if (rc) return rc;
+    m->rep_t[(size_t)m->sel] = m->t; m->rep_hist[(size_t)m->sel] = m->n_hist;
+    lda_load_replica(m, r);
+    return MMM_OK;
+}
+
+int mmm_lda_fit_batch(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged, double* elbo)
+{
+    if (!m || !n_iter || !converged) return MMM_ERR_ARG;
+    mmm_ctx* ctx = m->ctx;
+    if (m->ilda) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_fit_batch: ILDA handles have no restart batches (fit them with mmm_lda_fit)");
+    if (m->R == 1) return mmm_lda_fit(m, maxiter, tol, ll_hist, n_iter, converged, elbo);
+    MMM_CHECK(ctx, maxiter >= 1, "mmm_lda_fit_batch: maxiter < 1");
+    int rc = prepare_call(m);
+    if (rc) return rc;
+    const int R = m->R, keep = m->sel;
+    m->rep_t[(size_t)keep] = m->t; m->rep_hist[(size_t)keep] = m->n_hist;
+    for (int r = 1; r < R; ++r)
+        if (m->rep_t[(size_t)r] != m->rep_t[0] || m->rep_hist[(size_t)r] != m->rep_hist[0])
+            return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_fit_batch: the replicas stand at different passes (replica %d: %d, replica 0: %d) after an "
+                            "earlier fit_batch stopped them apart -- fit further on single handles", r, m->rep_t[(size_t)r], m->rep_t[0]);
+    lda_load_replica(m, 0);
+    if ((rc = ensure_hist(m, maxiter))) return rc;
+    hipLaunchKernelGGL(k_ctl_clear_stop_batch, dim3(R), dim3(1), 0, ctx->stream, m->ctl.p);
+    MMM_LAUNCH_CHECK(ctx);
+    m->stop_seen = false;
+    const int base = m->n_hist;
+    // chunks of passes pipelined as in run_chunks_pipelined: the host looks at chunk i's snapshot of the R control blocks once chunk i+1 is
+    // enqueued, and stops enqueueing when every replica has met its stopping rule
+    if (!m->pin.p) MMM_HIP(ctx, hipHostMalloc((void**)&m->pin.p, sizeof(LdaCtl) * 2 * R, hipHostMallocDefault));
+    for (int i = 0; i < 2; ++i) if (!ctx->pin_ev[i]) MMM_HIP(ctx, hipEventCreateWithFlags(&ctx->pin_ev[i], hipEventDisableTiming));
+    int enq = 0, slot = 0;
+    bool have_prev = false;
+    while (enq < maxiter) {
+        const int chunk = std::min(maxiter - enq, enq == 0 ? 12 : 8);
+        if ((rc = batch_passes(m, chunk, tol, base))) return rc;
+        enq += chunk;
+        MMM_HIP(ctx, hipMemcpyAsync(m->pin.p + (size_t)slot * R, m->ctl.p, sizeof(LdaCtl) * R, hipMemcpyDeviceToHost, ctx->stream));
+        MMM_HIP(ctx, hipEventRecord(ctx->pin_ev[slot], ctx->stream));
+        if (have_prev) {
+            MMM_HIP(ctx, hipEventSynchronize(ctx->pin_ev[slot ^ 1]));
+            const LdaCtl* prev = m->pin.p + (size_t)(slot ^ 1) * R;
+            bool all = true;
+            for (int r = 0; r < R && all; ++r) all = prev[r].stop != 0;
+            if (all) break;
+        }
+        have_prev = true; slot ^= 1;
+    }
+    std::vector<LdaCtl> h((size_t)R);
+    MMM_HIP(ctx, hipMemcpyAsync(h.data(), m->ctl.p, sizeof(LdaCtl) * R, hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    m->inflight = false;
+    std::vector<char> stopped((size_t)R);
+    for (int r = 0; r < R; ++r) { stopped[(size_t)r] = h[(size_t)r].stop != 0; m->rep_t[(size_t)r] = h[(size_t)r].t; m->rep_hist[(size_t)r] = h[(size_t)r].n_hist; }
+    // replicas that ran maxiter passes: the ll of their last pass is still pending and its convergence test is done here (mmm_lda_fit)
+    for (int r = 0; r < R; ++r) {
+        if (stopped[(size_t)r]) continue;
+        lda_load_replica(m, r);
+        m->ll_pending = true;
+        if ((rc = flush_ll(m, nullptr))) return rc;
+        m->rep_hist[(size_t)r] = m->n_hist;
+    }
+    m->ll_pending = false;
+    const size_t cap = (size_t)m->cap_hist;
+    std::vector<double> hh((size_t)R * cap);
+    MMM_HIP(ctx, hipMemcpyAsync(hh.data(), m->ll_hist.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < R; ++r) {
+        const int n = m->rep_hist[(size_t)r] - base;
+        const double* ll = hh.data() + (size_t)r * cap + base;
+        n_iter[r] = n;
+        converged[r] = stopped[(size_t)r] || (n > 10 && fabs(ll[n - 2] - ll[n - 1]) / fabs(ll[n - 1]) < tol) ? 1 : 0;
+        if (ll_hist && n > 0) memcpy(ll_hist + (size_t)r * maxiter, ll, sizeof(double) * n);
+    }
+    if (elbo) {      // every replica's ELBO enqueued back to back (phi formed for each in turn), one wait
+        double* acc = m->elbopart.p + (size_t)m->grid_s * 5;
+        for (int r = 0; r < R; ++r) {
+            lda_load_replica(m, r);
+            if ((rc = materialise_phi(m)) || (rc = lda_elbo_enqueue(m, acc + 8 * (size_t)r))) {
+                (void)hipStreamSynchronize(ctx->stream);
+                return rc;
+            }
+        }
+        std::vector<double> ha((size_t)8 * R);
+        MMM_HIP(ctx, hipMemcpyAsync(ha.data(), acc, sizeof(double) * ha.size(), hipMemcpyDeviceToHost, ctx->stream));
+        MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int r = 0; r < R; ++r) lda_elbo_finish(m, ha.data() + 8 * (size_t)r, &elbo[r], nullptr);
+    }
+    lda_load_replica(m, keep);
     return MMM_OK;
 }
 

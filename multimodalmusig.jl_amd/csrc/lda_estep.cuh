@@ -59,7 +59,8 @@ __device__ __forceinline__ void lda_chunk(const int2 tcv, const bool act, const 
 }
 
 // SINGLE: the grid covers every document with one step per wave (no step loop: 46 VGPRs less -> 3 waves per SIMD)
-template <int KP, int L, bool LL, int VT, bool SINGLE>
+// RB: batch build, replica blockIdx.y (rep())
+template <int KP, int L, bool LL, int VT, bool SINGLE, bool RB = false>
 __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 2) void k_lda_estep(EstepArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -67,13 +68,18 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     constexpr int PRE = (96 + L - 1) / L;             // chunks prefetched into registers (covers a 96-term document)
     MMM_STAMP(0);
     const int t = a.t;
-    const int stop = a.ctl->stop;                     // consumed after the first prologue (its latency is hidden)
+    const int stop = rep<RB>(a.ctl, 1)->stop;         // consumed after the first prologue (its latency is hidden)
     const double* __restrict__ gam = a.gamma.s[t % 3];
     const double* __restrict__ gprev = a.gamma.s[(t + 2) % 3];
     double* __restrict__ gnext = a.gamma.s[(t + 1) % 3];
     double* __restrict__ Eln = a.Elntheta.s[t % 3];
     const double* __restrict__ eB = a.expElnbeta.s[(t + 2) % 3];
     const double* __restrict__ bprev = a.beta.s[(t + 2) % 3];
+    if constexpr (RB) {
+        const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
+        gam = rep<RB>(gam, KD); gprev = rep<RB>(gprev, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD);
+        eB = rep<RB>(eB, VK); bprev = rep<RB>(bprev, VK);
+    }
 
     const int K = a.c.K, D = a.c.D;
     const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
@@ -97,7 +103,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     bool valid = d < D;
     // ext: this pass's prologue (digamma, exp: 2 us of this kernel's 10 at BASELINE config 2, all of it on every wave's dependent chain)
     // has run beside the previous pass's reduction, off the critical path; the same functions on the same lanes, hence the same bits
-    const bool ext = SINGLE && !LL && a.aexp != nullptr;
+    const bool ext = SINGLE && !LL && !RB && a.aexp != nullptr;      // (batches have no merged launch, so no prologue formed ahead)
     double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
     double gp = (LL && valid && l < K) ? gprev[(size_t)d * K + l] : (l < K ? 1.0 : 0.0);
     // Single-step build over padded rows (c.ell: [D][V] (term,count), (-1,0) past the document's end): the document's pairs are
@@ -321,6 +327,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     __syncthreads();
     if (LL && lane == 0) sA[wid] = ll_acc;      // sA is free now
     double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
+    if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
     for (int i = tid; i < K * V; i += blockDim.x) {
         double v8[kMaxWavesE];
 #pragma unroll
@@ -335,7 +342,8 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
         if (tid == 0) {
             double s = 0.0;
             for (int w = 0; w < NW; ++w) s += sA[w];
-            a.llpart[blockIdx.x] = s;
+            if constexpr (RB) a.llpart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+            else a.llpart[blockIdx.x] = s;
         }
     }
     MMM_STAMP(7);
@@ -354,18 +362,22 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
 template <class T> __device__ __forceinline__ T* at_byte(T* base, unsigned off) { return (T*)((char*)base + off); }   // uniform base + 32-bit lane offset: one VGPR per address
 typedef unsigned short mmm_us2 __attribute__((ext_vector_type(2)));
 
-template <int KP, int SL, bool C16>
+template <int KP, int SL, bool C16, bool RB = false>
 __global__ __launch_bounds__(512, 2) void k_lda_estep_dense(EstepArgs a, const int* __restrict__ cnt, const unsigned short* __restrict__ cnt16)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int L = 16, G = MMM_WAVE / L, Vp = L * SL;
     MMM_STAMP(0);
     const int t = a.t;
-    const int stop = a.ctl->stop;
+    const int stop = rep<RB>(a.ctl, 1)->stop;
     const double* __restrict__ gam = a.gamma.s[t % 3];
     double* __restrict__ gnext = a.gamma.s[(t + 1) % 3];
     double* __restrict__ Eln = a.Elntheta.s[t % 3];
     const double* __restrict__ eB = a.expElnbeta.s[(t + 2) % 3];
+    if constexpr (RB) {
+        const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
+        gam = rep<RB>(gam, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD); eB = rep<RB>(eB, VK);
+    }
     const int K = a.c.K, D = a.c.D, V = a.c.V;
     const int NW = blockDim.x >> 6;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -530,6 +542,7 @@ __global__ __launch_bounds__(512, 2) void k_lda_estep_dense(EstepArgs a, const i
     __syncthreads();
     MMM_STAMP(5);
     double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
+    if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
     for (int i = tid; i < K * V; i += blockDim.x) {
         const int kk = i / V, v = i - kk * V;
         double s = 0.0;

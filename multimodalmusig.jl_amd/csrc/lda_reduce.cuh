@@ -6,6 +6,7 @@ struct ReduceArgs {
     double* stats;         // out: [VK] summed lambda statistics of pass t, [VK] ll numerator of pass t-1
     LdaCtl* ctl;
     int t;                 // this pass (host count)
+    int hist_stride;       // batch launches: ll_hist doubles per replica (rep_reduce)
     double Nglobal, tol;
     double* ll_hist;
     int do_ll, conv_base, run_tail;
@@ -19,6 +20,18 @@ struct ReduceArgs {
     // numerators inside the reduce launch, through seq-tagged cells (as k_lda_reduce_ll_mstep does); the tail then only finishes
     unsigned long long* ll_cells; unsigned int ll_seq;
 };
+
+// replica blockIdx.y's view of the arguments of a batched split launch (k_lda_reduce[_ll], k_lda_mstep): the per-replica arrays are
+// sized from the launch itself -- nslab x VK partials, nslab E-step ll partials, VK + 16 statistics, 512 ll-block numerators
+template <bool RB>
+__device__ __forceinline__ void rep_reduce(ReduceArgs& r)
+{
+    if constexpr (RB) {
+        const size_t y = blockIdx.y;
+        r.partial += y * r.nslab * r.VK; r.llpart += y * r.nslab; r.stats += y * (r.VK + 16);
+        r.ctl += y; r.ll_hist += y * r.hist_stride; r.llpart2 += y * 512;
+    }
+}
 
 // ll_{t-1}, the convergence test of common.jl:53-56 after > 10 values (LDA.jl:215) and t += 1 (one thread)
 __device__ void lda_pass_tail(const ReduceArgs& r)
@@ -297,14 +310,23 @@ __device__ void lda_reduce_block(const ReduceArgs& r)
     }
 }
 
-__global__ __launch_bounds__(1024) void k_lda_reduce(ReduceArgs r) { lda_reduce_block(r); }
+template <bool RB = false>
+__global__ __launch_bounds__(1024) void k_lda_reduce(ReduceArgs r)
+{
+    if constexpr (RB) rep_reduce<RB>(r);
+    lda_reduce_block(r);
+}
 
 // the same launch with the ll of pass t-1 riding along: blocks [0, nred) are k_lda_reduce's, blocks [nred, gridDim) evaluate the
 // log-likelihood numerators while the reduction -- 60 blocks -- leaves most of the chip idle
-template <int KP>
+template <int KP, bool RB = false>
 __global__ __launch_bounds__(1024) void k_lda_reduce_ll(ReduceArgs r, LdaDev c, const double* gprev, const double* bprev, double* llpart2, int nred)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    if constexpr (RB) {
+        rep_reduce<RB>(r);
+        gprev = rep<RB>(gprev, (size_t)c.K * c.D); bprev = rep<RB>(bprev, (size_t)c.V * c.K); llpart2 = rep<RB>(llpart2, 512);
+    }
     if ((int)blockIdx.x < nred) { lda_reduce_block(r); return; }
     if (r.ctl->stop) return;
     constexpr int L = KP <= 15 ? 16 : (KP <= 31 ? 32 : 64);       // K <= KP: the E-step's lane-group width (K = 16 -> KP = 16 -> 32 lanes)
@@ -541,9 +563,10 @@ __global__ __launch_bounds__(1024) void k_lda_reduce_ll_mstep(ReduceArgs r, LdaD
 // Blocks of two waves: with the mailbox exchange folded in, both waves receive (V <= 128 entries in ONE polling round);
 // wave 0 alone then runs the topic's M-step.
 // P2P = false: the build without the mailbox code (its polling arrays live in scratch memory; a single-GPU launch carries none).
-template <bool P2P>
+template <bool P2P, bool RB = false>
 __global__ __launch_bounds__(128) void k_lda_mstep(ReduceArgs r, int V, double eta, Ring lambda, Ring Elnbeta, Ring expElnbeta, Ring beta)
 {
+    if constexpr (RB) rep_reduce<RB>(r);
     const int stop = r.ctl->stop;
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, c = r.t % 3;
     if (k == (int)gridDim.x - 1) {      // the extra block: pass tail, concurrent with the topic blocks (its loads are a dependent chain)
@@ -562,6 +585,17 @@ __global__ __launch_bounds__(128) void k_lda_mstep(ReduceArgs r, int V, double e
     if (stop) return;
     const double cs = wave_sum(part);
     const double psi = dev_digamma_pos(cs);
+    if constexpr (RB) {      // the slot's arrays of replica blockIdx.y (K topic blocks + the tail block; a Ring offset in place would be indexed from scratch)
+        const size_t VK = (size_t)V * (gridDim.x - 1);
+        double* lam = rep<RB>(lambda.s[c], VK); double* Eln = rep<RB>(Elnbeta.s[c], VK); double* eEln = rep<RB>(expElnbeta.s[c], VK); double* bet = rep<RB>(beta.s[c], VK);
+        for (int v = tid; v < V; v += 128) {
+            const double l = eta + sums[v];
+            const double el = dev_digamma_pos(l) - psi;
+            const size_t e = (size_t)k * V + v;
+            lam[e] = l; Eln[e] = el; eEln[e] = exp(el); bet[e] = l / cs;
+        }
+        return;
+    }
     for (int v = tid; v < V; v += 128) {
         const double l = eta + sums[v];
         const double el = dev_digamma_pos(l) - psi;

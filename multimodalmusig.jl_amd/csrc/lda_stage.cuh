@@ -540,6 +540,8 @@ __global__ void k_ll_push(LdaCtl* ctl, const double* num, double N, double* hist
 }
 
 __global__ void k_ctl_clear_stop(LdaCtl* ctl) { ctl->stop = 0; ctl->stop_iter = 0; ctl->ticket = 0; }
+// the same for the R control blocks of a batch handle (grid R)
+__global__ void k_ctl_clear_stop_batch(LdaCtl* ctl) { ctl += blockIdx.x; ctl->stop = 0; ctl->stop_iter = 0; ctl->ticket = 0; }
 
 // gamma[:,d] = alpha + phi[d] * n_d (LDA.jl:83-87) from a resident phi, then Elntheta (if asked)
 __global__ __launch_bounds__(kBlock) void k_lda_gamma_from_phi(LdaDev c, const double* phi, double* gamma, double* Elntheta)

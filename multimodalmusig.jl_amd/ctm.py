@@ -535,13 +535,17 @@ def _fit_ctm(model, maxiter, tol, verbose, autoα=False, updateΣ=True):
     return hist
 
 
-def fit_restarts(model, maxiter=100, tol=1e-4, verbose=False, updateΣ=True, autoα=False):
+def fit_restarts(model, maxiter=None, tol=1e-4, verbose=False, updateΣ=True, autoα=False):
     """`fit!` of every restart of a batch model (constructed with `restarts=R` or R stacked γ0), all restarts advancing
     together on the GPU -- what `fit_seed_models` (scripts/run_mmctm.jl:97-109) gets from `pmap(fit_restart, seeds)`.
     Returns the list of per-restart ll histories ([n_iter_r, M] each); per-restart results are kept on the model as
-    `restart_ll` ([R, M] final ll), `restart_elbo`, `restart_converged`, `restart_iters`."""
+    `restart_ll` ([R, M] final ll), `restart_elbo`, `restart_converged`, `restart_iters`.  maxiter defaults to fit!'s: 100 here,
+    1000 for an `LDA(..., restarts=R)`, which is dispatched to its own batch fit (models._fit_restarts_lda; [n_iter_r] histories)."""
+    from .models import LDA, _fit_restarts_lda
+    if isinstance(model, LDA):
+        return _fit_restarts_lda(model, maxiter=1000 if maxiter is None else maxiter, tol=tol, verbose=verbose)
     R, M = model.R, model.M
-    maxiter = int(maxiter)
+    maxiter = 100 if maxiter is None else int(maxiter)
     ll = np.zeros(R * maxiter * M); ni = np.zeros(R, dtype=np.int32); cv = np.zeros(R, dtype=np.int32); el = np.zeros(R)
     check(lib().mmm_ctm_fit_batch(model._h, maxiter, float(tol), _fit_flags(autoα, updateΣ), ll.ctypes.data, ni.ctypes.data, cv.ctypes.data, el.ctypes.data),
           model.ctx.h, "fit_restarts(::%s)" % type(model).__name__)

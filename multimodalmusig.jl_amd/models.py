@@ -44,9 +44,13 @@ class LDA:
     X: list of (W_d x 2) integer matrices `[term(1-based) count]` as produced by `format_counts_lda`.
     The random init `λ = rand(1:100, V, K)` (LDA.jl:36) is drawn with numpy (`seed`) unless `λ0` is given.
     With a multi-rank Context, X is this rank's shard of the documents.
+
+    `restarts=R`: one handle holding R models over the one resident corpus (mmm_lda_create_batch), fitted together by
+    `fit_restarts`.  `λ0` is then a sequence of R V x K inits, or absent: restart r is drawn as `LDA(..., seed=seed + r)` would draw
+    it.  The fields read the selected restart (`select(r)`, 0 at first).
     """
 
-    def __init__(self, k, α, η, *args, λ0=None, seed=None, ctx=None):
+    def __init__(self, k, α, η, *args, λ0=None, seed=None, ctx=None, restarts=None):
         if len(args) == 1:
             V, X = None, args[0]
         elif len(args) == 2:
@@ -60,17 +64,35 @@ class LDA:
             V = int(self._term.max()) + 1 if self._term.size else 0     # LDA.jl:57-66
         self.V = int(V)
         self.N = np.array([int(self._count[self._doc_ptr[d]:self._doc_ptr[d + 1]].sum()) for d in range(self.D)], dtype=np.int64)
-        if λ0 is None:
-            λ0 = np.random.default_rng(seed).integers(1, 101, size=(self.V, self.K)).astype(np.float64)
-        λ0 = np.asarray(λ0, dtype=np.float64)
-        if λ0.shape != (self.V, self.K):
-            raise ValueError("λ0 must be V x K")
+        def draw(sd):
+            return np.random.default_rng(sd).integers(1, 101, size=(self.V, self.K)).astype(np.float64)
+
+        def flat(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.shape != (self.V, self.K):
+                raise ValueError("λ0 must be V x K")
+            return x.ravel(order="F")
         self.ctx = ctx or _lib.default_context()
         self._h = C.c_void_p()
+        self._sel = 0
         tp = self._term.ctypes.data if self._term.size else None
         cp = self._count.ctypes.data if self._count.size else None
-        check(lib().mmm_lda_create(self.ctx.h, self.D, self.V, self.K, self.α, self.η, self._doc_ptr, tp, cp,
-                                   np.ascontiguousarray(λ0.ravel(order="F")), C.byref(self._h)), self.ctx.h, "mmm_lda_create")
+        if restarts is None:
+            self.R = 1
+            check(lib().mmm_lda_create(self.ctx.h, self.D, self.V, self.K, self.α, self.η, self._doc_ptr, tp, cp,
+                                       np.ascontiguousarray(flat(draw(seed) if λ0 is None else λ0)), C.byref(self._h)), self.ctx.h, "mmm_lda_create")
+        else:
+            R = int(restarts)
+            if λ0 is None:
+                λ0 = [draw(None if seed is None else seed + r) for r in range(max(R, 0))]
+            if len(λ0) != max(R, 0):
+                raise ValueError("restarts=%d but %d initialisations given" % (R, len(λ0)))
+            lam = np.concatenate([flat(x) for x in λ0]) if R > 0 else np.zeros(1)
+            self.R = R
+            check(lib().mmm_lda_create_batch(self.ctx.h, R, self.D, self.V, self.K, self.α, self.η, self._doc_ptr, tp, cp,
+                                             np.ascontiguousarray(lam), C.byref(self._h)), self.ctx.h, "mmm_lda_create_batch")
+        self._hyper0 = (self.α, self.η)
+        self.restart_ll = None; self.restart_elbo = None; self.restart_converged = None; self.restart_iters = None
         _lib.track(self)
         self.converged = False
         self.elbo = float("nan")
@@ -94,9 +116,25 @@ class LDA:
     def _mat(self, name, rows, cols):
         return self._get(name).reshape(rows, cols, order="F")
 
+    # ---- restart batch ---------------------------------------------------------------------------------------
+    def select(self, r):
+        """Make restart `r` the model the fields and the per-model functions act on."""
+        check(lib().mmm_lda_select(self._h, int(r)), self.ctx.h, "select")
+        self._sel = int(r)
+        return self
+
+    @property
+    def selected(self):
+        return self._sel
+
     def _push_hyper(self):
         """`model.α` / `model.η` are plain mutable fields upstream (LDA.jl:7,11; ILDA.jl:8,12): what the caller has assigned goes to the
-        device before any function that reads them (mmm_lda_set_hyper does nothing when they are unchanged)."""
+        device before any function that reads them (mmm_lda_set_hyper does nothing when they are unchanged).  A restart batch keeps
+        the values it was created with."""
+        if getattr(self, "R", 1) > 1:
+            if (self.α, self.η) != self._hyper0:
+                raise ValueError("model.α / model.η of a restart batch are fixed at construction (create a new LDA(..., restarts=R))")
+            return
         eta = np.ascontiguousarray(np.atleast_1d(np.asarray(self.η, dtype=np.float64)))
         check(lib().mmm_lda_set_hyper(self._h, float(self.α), eta, int(eta.size)), self.ctx.h, "mmm_lda_set_hyper")
 
@@ -211,6 +249,7 @@ class ILDA(LDA):
         self._h = C.c_void_p()
         tp = self._term.ctypes.data if self._term.size else None
         cp = self._count.ctypes.data if self._count.size else None
+        self.R, self._sel = 1, 0                                                                 # (no ILDA restart batches)
         feat = np.ascontiguousarray((f - 1).T.ravel(), dtype=np.int32)                         # [i*V + v], 0-based
         check(lib().mmm_ilda_create(self.ctx.h, self.D, self.V, self.K, self.α, self.I, np.ascontiguousarray(self.J, dtype=np.int32),
                                     np.ascontiguousarray(self.η), feat, self._doc_ptr, tp, cp, lam0, C.byref(self._h)), self.ctx.h, "mmm_ilda_create")
@@ -310,6 +349,8 @@ def fit(model, maxiter=None, tol=1e-4, verbose=True, **kw):
     """`fit!(model; maxiter, tol, verbose)` -- LDA.jl:198-224 (maxiter default 1000), MMCTM.jl:457-494 and
     IMMCTM.jl:437-466 (default 100).  Returns the log-likelihood history and sets converged/elbo/ll."""
     if isinstance(model, LDA):
+        if getattr(model, "R", 1) > 1:
+            raise ValueError("fit: this LDA holds %d restarts; fit them together with fit_restarts(model)" % model.R)
         maxiter = 1000 if maxiter is None else int(maxiter)
         model._push_hyper()
         ll = np.zeros(maxiter); ni = C.c_int(); cv = C.c_int(); el = C.c_double()
@@ -326,3 +367,23 @@ def fit(model, maxiter=None, tol=1e-4, verbose=True, **kw):
 
 
 fit_bang = fit   # `fit!`
+
+
+def _fit_restarts_lda(model, maxiter=1000, tol=1e-4, verbose=False):
+    """`fit!` of every restart of an `LDA(..., restarts=R)` (mmm_lda_fit_batch): all restarts advance together on the GPU, each
+    stops by its own rule.  Returns the list of per-restart ll histories and keeps `restart_ll` ([R] final ll), `restart_elbo`,
+    `restart_converged`, `restart_iters` on the model; `converged` / `elbo` / `ll` are the selected restart's."""
+    R, maxiter = model.R, int(maxiter)
+    model._push_hyper()
+    ll = np.zeros(R * maxiter); ni = np.zeros(R, dtype=np.int32); cv = np.zeros(R, dtype=np.int32); el = np.zeros(R)
+    check(lib().mmm_lda_fit_batch(model._h, maxiter, float(tol), ll.ctypes.data, ni.ctypes.data, cv.ctypes.data, el.ctypes.data),
+          model.ctx.h, "fit_restarts(::%s)" % type(model).__name__)
+    hists = [ll[r * maxiter:r * maxiter + ni[r]].copy() for r in range(R)]
+    model.restart_ll = np.array([h[-1] if h.size else np.nan for h in hists])
+    model.restart_elbo = el.copy(); model.restart_converged = cv.astype(bool); model.restart_iters = ni.copy()
+    if verbose:
+        for r in range(R):
+            print("restart %d\t%d iterations\tLog-likelihood: %r" % (r, ni[r], float(model.restart_ll[r])))
+    s = model.selected
+    model.converged = bool(cv[s]); model.elbo = float(el[s]); model.ll = float(model.restart_ll[s])
+    return hists

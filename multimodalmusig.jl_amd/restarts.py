@@ -15,7 +15,8 @@ Differences that do not change results:
 import numpy as np
 
 from .ctm import MMCTM, fit_restarts, pick_optimal_modality_models
-from .models import fit
+from .models import LDA, fit
+from .utils import pack_lda
 
 
 def dense_rank(x):
@@ -79,6 +80,58 @@ def fit_seed_models(counts, K, α, V, seeds, batch_size=None, ctx=None, maxiter=
                 best_gamma[m] = np.stack([model.γ[m][k] for k in range(K[m])])
         model.close()
     return best_gamma, best_ll, all_ll
+
+
+def _best(ll):
+    """Index of the highest final log-likelihood; ties go to the lowest index, a NaN never wins."""
+    ll = np.asarray(ll, dtype=np.float64)
+    return int(np.argmax(np.where(np.isnan(ll), -np.inf, ll)))
+
+
+def fit_lda_restarts(X, K, α, η, seeds, V=None, batch_size=None, ctx=None, maxiter=1000, tol=1e-4, rank=0, nranks=1, allgather=None):
+    """LDA from several random initialisations, keeping the best: restart i is `LDA(K, α, η, [V,] X, seed=seeds[i])`, fitted with
+    the others as the replicas of batch handles of at most `batch_size` restarts (all of them by default).  Returns (index of the
+    restart with the highest final log-likelihood -- ties to the lowest index --, its λ (V x K), its γ (K x D), the [len(seeds)]
+    final log-likelihoods).
+
+    Several GPUs: as fit_seed_models -- rank r of nranks fits seeds[r::nranks] on its own context (without a communicator) and
+    the results are merged with the host's `allgather(obj) -> list of every rank's obj`; every rank returns the same."""
+    seeds = [int(s) for s in seeds]
+    if nranks > 1:
+        if allgather is None:
+            raise ValueError("nranks > 1 needs an allgather callable")
+        mine = seeds[rank::nranks]
+        res = fit_lda_restarts(X, K, α, η, mine, V=V, batch_size=batch_size, ctx=ctx, maxiter=maxiter, tol=tol) if mine else (
+            None, None, None, np.zeros(0))
+        parts = allgather(res)
+        merged = np.full(len(seeds), np.nan)
+        for r, part in enumerate(parts):
+            merged[r::nranks] = part[3]
+        win = _best(merged)
+        # the winner's rank picked it too: within a rank the restarts keep their global order, so its first maximum is the global one
+        part = parts[win % nranks]
+        return win, part[1], part[2], merged
+    if V is None:
+        term = pack_lda(X)[1]
+        V = int(term.max()) + 1 if term.size else 0                  # LDA.jl:57-66
+    R = len(seeds)
+    if R == 0:
+        raise ValueError("fit_lda_restarts: no seeds")
+    bs = R if not batch_size else int(batch_size)
+    all_ll = np.full(R, np.nan)
+    best = None
+    for b0 in range(0, R, bs):
+        chunk = seeds[b0:b0 + bs]
+        lam0 = [np.random.default_rng(s).integers(1, 101, size=(V, K)).astype(np.float64) for s in chunk]   # LDA(..., seed=s), LDA.jl:36
+        model = LDA(K, α, η, V, X, λ0=lam0, restarts=len(chunk), ctx=ctx)
+        fit_restarts(model, maxiter=maxiter, tol=tol)
+        all_ll[b0:b0 + len(chunk)] = model.restart_ll
+        i = _best(model.restart_ll)
+        if best is None or _best([all_ll[best[0]], model.restart_ll[i]]) == 1:    # (an equal later batch keeps the earlier index)
+            model.select(i)
+            best = (b0 + i, model.λ, model.γ)
+        model.close()
+    return best[0], best[1], best[2], all_ll
 
 
 def seed_and_fit_restart(counts, K, α, V, opt_gamma, ctx=None, maxiter=1000, tol=1e-5, **kw):

@@ -299,9 +299,22 @@ int mmm_ctm_update_alpha(mmm_ctm* m);   /* update_α! (1-D LD_MMA per α) MMCTM.
 int mmm_ctm_update_props(mmm_ctm* m);   /* update_props!                MMCTM.jl:145-154              */
 int mmm_ctm_update_phi(mmm_ctm* m);     /* update_ϕ!                    MMCTM.jl:244-250              */
 /* The reference's per-document functions take the document: update_ζ!(model, d), update_θ!(model, d), update_ν!(model, d),
- * update_λ!(model, d) (MMCTM.jl:127-198; test/mmctm.jl:92-199 call them that way).  Only document d (0-based) changes. */
-enum { MMM_STAGE_ZETA = 0, MMM_STAGE_THETA = 1, MMM_STAGE_NU = 2, MMM_STAGE_LAMBDA = 3 };
+ * update_λ!(model, d), fitdoc!(model, d) (MMCTM.jl:127-198, 450-455; test/mmctm.jl:92-199 call them that way).
+ * mmm_ctm_update_docs runs a stage on the n documents docs[0..n) (0-based ids of this rank's shard, distinct, any order) of the selected
+ * replica.  MMM_STAGE_FITDOC = ζ, θ, ν, λ in that order, one wait.  Every listed document gets, bit for bit, what the whole-corpus stage
+ * call(s) write for it on this handle (λ, ν, ζ, θ, sumθ, its evaluation counters); every other document keeps its values and counters.
+ * Device work is the listed documents' (plus an O(n) upload of the list; theta of the replica is formed first if it is held implicitly).
+ * MMM_ERR_ARG, before anything runs and with nothing changed: unknown stage, n < 0, docs == NULL with n > 0, an id outside [0, D), an id
+ * listed twice.  n == 0: nothing.  Not collective.  mmm_ctm_update_doc(m, stage, d) = mmm_ctm_update_docs(m, stage, &d, 1). */
+enum { MMM_STAGE_ZETA = 0, MMM_STAGE_THETA = 1, MMM_STAGE_NU = 2, MMM_STAGE_LAMBDA = 3, MMM_STAGE_FITDOC = 4 };
+int mmm_ctm_update_docs(mmm_ctm* m, int stage, const int32_t* docs, int n);
 int mmm_ctm_update_doc(mmm_ctm* m, int stage, int d);
+/* Document d's part of a per-document field of the selected replica, without a whole-field transfer: MMM_CTM_LAMBDA, _NU, _PROPS (sum K
+ * values), _ZETA (M), _THETA (the K_m x W_dm block of every modality, modality-major, each in the flat field's layout: sum_m K_m W_dm
+ * values).  n must be that count; other fields: MMM_ERR_ARG.  set_doc of THETA changes no other document's theta (the replica's theta is
+ * formed first if it is held implicitly, and is explicit afterwards, as after mmm_ctm_set). */
+int mmm_ctm_get_doc(mmm_ctm* m, int field, int d, double* host, size_t n);
+int mmm_ctm_set_doc(mmm_ctm* m, int field, int d, const double* host, size_t n);
 /* calculate_sumθ(model, d) and calculate_Ndivζ(model, d) -- MMCTM.jl:110-125 / IMMCTM.jl:90-105: sum K doubles each (either may be NULL),
  * from the stored θ and ζ of document d (0-based) */
 int mmm_ctm_doc_sums(mmm_ctm* m, int d, double* sumtheta, double* Ndivzeta);

@@ -122,6 +122,9 @@ _SIGS = {
     "mmm_lda_update_Elntheta": (C.c_int, [vp]),
     "mmm_lda_update_Elnbeta": (C.c_int, [vp]),
     "mmm_ctm_update_doc": (C.c_int, [vp, C.c_int, C.c_int]),
+    "mmm_ctm_update_docs": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+    "mmm_ctm_get_doc": (C.c_int, [vp, C.c_int, C.c_int, f64p, C.c_size_t]),
+    "mmm_ctm_set_doc": (C.c_int, [vp, C.c_int, C.c_int, f64p, C.c_size_t]),
     "mmm_ctm_doc_sums": (C.c_int, [vp, C.c_int, vp, vp]),
     "mmm_lambda_objective": (C.c_int, [vp, C.c_int, f64p, f64p, f64p, f64p, f64p, f64p, C.POINTER(C.c_double), vp]),
     "mmm_nu_objective": (C.c_int, [vp, C.c_int, f64p, f64p, f64p, vp, f64p, C.POINTER(C.c_double), vp]),

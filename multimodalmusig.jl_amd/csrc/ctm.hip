@@ -21,6 +21,7 @@
 //
 // The MMA solves restate NLopt's LD_MMA for zero constraints (algorithm statement: DESIGN.md "MMA" and
 // SURVEY.md §7): one objective evaluation per trip of a single wave-uniform loop, per-group state, select-based commits.
+#include <algorithm>
 #include <memory>
 #include "dev_math.h"
 #include "mmm_logtab.h"
@@ -86,6 +87,8 @@ struct mmm_ctm {
     DevBuf<double> mu, Sigma, invSigma, gamma, Elnphi, phi, Eeff, expEeff, expEeff_prev, phieff;   // [R][...]
     DevBuf<double> partial, mompart, stats, llpart, llnum, Nm, elbopart, ll_hist;
     DevBuf<int> nev_nu, nev_lam, status, active, npass;
+    DevBuf<int> doclist;                       // the document list of the last mmm_ctm_update_docs call (grown on demand)
+    std::vector<int64_t> h_doc_ptr;            // host copy of doc_ptr: the per-document spans of theta (mmm_ctm_get_doc / set_doc)
     // dense corpora: the fused pass's theta phase over rows of 16-bit counts, one launch per modality (k_ctm_theta_dense)
     bool tdense = false; int tSL[kMaxM] = {0};
     DevBuf<unsigned short> trows[kMaxM];      // [D][16][SL_m rounded up to even]: lane-major rows of counts (a lane's part of a row is one load)
@@ -121,15 +124,47 @@ struct Scope { int rep0, nrep; const int* active; };
 inline Scope one(const mmm_ctm* m) { return Scope{m->sel, 1, nullptr}; }
 inline Scope all(const mmm_ctm* m) { return Scope{0, m->R, m->active.p}; }
 
-template <int L, int PH, int MKT = 0, int KMX = 16, int OCC = 4, bool WIDE = false, bool PACK = false>
-int launch_estep_L(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int waves, int nrep)
+// a stage kernel with the argument block -- and, in the document-list builds (DL), the list as its second argument
+template <bool DL, class K>
+int launch_k(mmm_ctx* ctx, K k, dim3 grid, dim3 block, size_t lds, const CtmEArgs& a, const DocList& dl)
 {
-    mmm_ctx* ctx = m->ctx;
-    auto k = k_ctm_estep<L, PH, MKT, KMX, OCC, WIDE, PACK>;
     if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(grid, nrep), dim3(waves * MMM_WAVE), lds, ctx->stream, a);
+    if constexpr (DL) hipLaunchKernelGGL(k, grid, block, lds, ctx->stream, a, dl);
+    else hipLaunchKernelGGL(k, grid, block, lds, ctx->stream, a);
     MMM_LAUNCH_CHECK(ctx);
     return MMM_OK;
+}
+
+// the whole-corpus build of a stage kernel, or its document-list build (parameter pack = one DocList)
+template <bool DL, int L, int PH, int MKT, int KMX, int OCC, bool WIDE, bool PACK>
+auto estep_kernel()
+{
+    if constexpr (DL) return k_ctm_estep<L, PH, MKT, KMX, OCC, WIDE, PACK, DocList>;
+    else return k_ctm_estep<L, PH, MKT, KMX, OCC, WIDE, PACK>;
+}
+template <bool DL, int MKT, int LPD, int OCC>
+auto solve_cpl_kernel()
+{
+    if constexpr (DL) return k_ctm_solve_cpl<MKT, LPD, OCC, false, DocList>;
+    else return k_ctm_solve_cpl<MKT, LPD, OCC, false>;
+}
+template <bool DL>
+auto theta_big_kernel()
+{
+    if constexpr (DL) return k_ctm_theta_big<DocList>;
+    else return k_ctm_theta_big<>;
+}
+template <bool DL>
+auto solve_big_kernel()
+{
+    if constexpr (DL) return k_ctm_solve_big<DocList>;
+    else return k_ctm_solve_big<>;
+}
+
+template <bool DL, int L, int PH, int MKT = 0, int KMX = 16, int OCC = 4, bool WIDE = false, bool PACK = false>
+int launch_estep_L(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int waves, int nrep, const DocList& dl)
+{
+    return launch_k<DL>(m->ctx, estep_kernel<DL, L, PH, MKT, KMX, OCC, WIDE, PACK>(), dim3(grid, nrep), dim3(waves * MMM_WAVE), lds, a, dl);
 }
 
 size_t estep_lds(const mmm_ctm* m, int flags)     // theta phase
@@ -196,55 +231,51 @@ int launch_theta_dense(mmm_ctm* m, const CtmEArgs& a, int nrep)
 }
 
 
-template <int PH>
-int launch_phase(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int waves, int nrep)
+// DL: a document-list launch (the list `dl`, grid sized from it by run_estep_docs).  Every choice of build below -- and so the
+// association of every document's arithmetic -- comes from the handle, never from the list: a listed document gets the bits the
+// whole-corpus launch gives it.
+template <int PH, bool DL = false>
+int launch_phase(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int waves, int nrep, const DocList& dl = DocList{nullptr, 0})
 {
     if (m->big) {      // sum K > 64: the generic kernels (ctm_big.cuh), one wave per document
         mmm_ctx* ctx = m->ctx;
-        const int nblk = std::max(1, std::min((m->dm.D + 3) / 4, mmm_geo_cus(ctx) * 4));
+        const int nblk = std::max(1, std::min(((DL ? dl.n : m->dm.D) + 3) / 4, mmm_geo_cus(ctx) * 4));
         if constexpr (PH == 0) {
             const size_t l = sizeof(double) * 4 * (64 + 64 * 64);
-            MMM_HIP(ctx, hipFuncSetAttribute((const void*)k_ctm_theta_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l));
-            hipLaunchKernelGGL(k_ctm_theta_big, dim3(nblk, nrep), dim3(256), l, ctx->stream, a);
+            MMM_HIP(ctx, hipFuncSetAttribute((const void*)theta_big_kernel<DL>(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l));
+            return launch_k<DL>(ctx, theta_big_kernel<DL>(), dim3(nblk, nrep), dim3(256), l, a, dl);
         } else {
-            const size_t l = sizeof(double) * 4 * (size_t)m->dm.MK;
-            hipLaunchKernelGGL(k_ctm_solve_big, dim3(nblk, nrep), dim3(256), l, ctx->stream, a);
+            return launch_k<DL>(ctx, solve_big_kernel<DL>(), dim3(nblk, nrep), dim3(256), sizeof(double) * 4 * (size_t)m->dm.MK, a, dl);
         }
-        MMM_LAUNCH_CHECK(ctx);
-        return MMM_OK;
     }
     if constexpr (PH == 1) {      // solve phase: compile-time sum K for the shapes of the BASELINE configs (cfg 5 / 3 / 4)
-        const bool small = (int64_t)grid * waves * nrep <= (int64_t)3 * 4 * mmm_geo_cus(m->ctx);      // cannot fill 4 waves per SIMD anyway
+        // (from the handle's whole-corpus solve launch, which is what every call but a document-list one launches)
+        const bool small = (int64_t)m->grid_v * m->waves_s * nrep <= (int64_t)3 * 4 * mmm_geo_cus(m->ctx);      // cannot fill 4 waves per SIMD anyway
         if (m->persist) {          // persistent waves with refilled document slots (several coordinates per lane, or one)
             mmm_ctx* ctx = m->ctx;
-            auto go = [&](auto kern) -> int {
-                if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, dim3(grid, nrep), dim3(waves * MMM_WAVE), lds, ctx->stream, a);
-                MMM_LAUNCH_CHECK(ctx);
-                return MMM_OK;
-            };
+            auto go = [&](auto kern) -> int { return launch_k<DL>(ctx, kern, dim3(grid, nrep), dim3(waves * MMM_WAVE), lds, a, dl); };
             // builds: sum K = 10 (BASELINE config 5) 2 lanes x 5 coordinates at 2 waves per SIMD, the chains of the coordinates interleaved by the
             // scheduler (245 VGPRs, no scratch); sum K = 28 (config 4) 16 lanes, 14 of them x 2 coordinates, at 3 waves per SIMD.  The other
             // layouts that were built and measured -- 8 x 4 and 32 x 1 for sum K = 28, 2 x 7 and 8 x 2 for sum K = 14, the two solves as two
             // launches with documents claimed on demand -- did not beat these and are gone from the source.
-            if (m->dm.MK == 10 && m->Ls == 2) return go(k_ctm_solve_cpl<10, 2, 2, false>);
-            if (m->dm.MK == 28 && m->Ls == 16) return go(k_ctm_solve_cpl<28, 16, 3, false>);
+            if (m->dm.MK == 10 && m->Ls == 2) return go(solve_cpl_kernel<DL, 10, 2, 2>());
+            if (m->dm.MK == 28 && m->Ls == 16) return go(solve_cpl_kernel<DL, 28, 16, 3>());
             // round 5, small shards (what one GPU of an N-GPU strong run holds): more lanes per document, so that the chip still has a wave per
             // SIMD and a document's chain of evaluations is shorter -- sum K = 10: 8 lanes, 5 of them x 2 coordinates (8 slots per wave instead
             // of 32); sum K = 28: 32 lanes x 1 coordinate (2 slots instead of 4)
-            if (m->dm.MK == 10 && m->Ls == 8) return go(k_ctm_solve_cpl<10, 8, 3, false>);
-            if (m->dm.MK == 28 && m->Ls == 32) return go(k_ctm_solve_cpl<28, 32, 4, false>);
+            if (m->dm.MK == 10 && m->Ls == 8) return go(solve_cpl_kernel<DL, 10, 8, 3>());
+            if (m->dm.MK == 28 && m->Ls == 32) return go(solve_cpl_kernel<DL, 28, 32, 4>());
             return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "no multi-coordinate solve build for sum K = %d", m->dm.MK);
         }
         if (m->Ls != m->L) {       // packed groups: sum K lanes per document
-            if (m->Ls == 6) return launch_estep_L<16, PH, 6, 16, 4, false, true>(m, a, lds, grid, waves, nrep);
-            if (m->Ls == 10) return launch_estep_L<16, PH, 10, 16, 4, false, true>(m, a, lds, grid, waves, nrep);
-            if (m->Ls == 12) return launch_estep_L<16, PH, 12, 16, 4, false, true>(m, a, lds, grid, waves, nrep);
+            if (m->Ls == 6) return launch_estep_L<DL, 16, PH, 6, 16, 4, false, true>(m, a, lds, grid, waves, nrep, dl);
+            if (m->Ls == 10) return launch_estep_L<DL, 16, PH, 10, 16, 4, false, true>(m, a, lds, grid, waves, nrep, dl);
+            if (m->Ls == 12) return launch_estep_L<DL, 16, PH, 12, 16, 4, false, true>(m, a, lds, grid, waves, nrep, dl);
             return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "no packed solve build for sum K = %d", m->Ls);
         }
-        if (m->L == 16 && m->dm.MK == 10) return small ? launch_estep_L<16, PH, 10, 16, 3>(m, a, lds, grid, waves, nrep) : launch_estep_L<16, PH, 10>(m, a, lds, grid, waves, nrep);
-        if (m->L == 16 && m->dm.MK == 14) return small ? launch_estep_L<16, PH, 14, 16, 3>(m, a, lds, grid, waves, nrep) : launch_estep_L<16, PH, 14>(m, a, lds, grid, waves, nrep);
-        if (m->L == 32 && m->dm.MK == 28) return small ? launch_estep_L<32, PH, 28, 16, 3>(m, a, lds, grid, waves, nrep) : launch_estep_L<32, PH, 28>(m, a, lds, grid, waves, nrep);
+        if (m->L == 16 && m->dm.MK == 10) return small ? launch_estep_L<DL, 16, PH, 10, 16, 3>(m, a, lds, grid, waves, nrep, dl) : launch_estep_L<DL, 16, PH, 10>(m, a, lds, grid, waves, nrep, dl);
+        if (m->L == 16 && m->dm.MK == 14) return small ? launch_estep_L<DL, 16, PH, 14, 16, 3>(m, a, lds, grid, waves, nrep, dl) : launch_estep_L<DL, 16, PH, 14>(m, a, lds, grid, waves, nrep, dl);
+        if (m->L == 32 && m->dm.MK == 28) return small ? launch_estep_L<DL, 32, PH, 28, 16, 3>(m, a, lds, grid, waves, nrep, dl) : launch_estep_L<DL, 32, PH, 28>(m, a, lds, grid, waves, nrep, dl);
     }
     if constexpr (PH == 0) {      // theta phase: a modality with more than 16 topics takes the build unrolled to 32
         int kmax = 0;
@@ -252,23 +283,23 @@ int launch_phase(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int waves,
         if (m->wide) {
             // 33..64 topics in one modality (sum K <= 64, so L = 64): the 64-topic build -- correct, far from tuned (its four 64-entry
             // register arrays live in scratch); the reference has no limit (MMCTM.jl:29-91)
-            if (kmax > 32) return launch_estep_L<64, PH, 0, 64, 4, true>(m, a, lds, grid, waves, nrep);
-            if (kmax > 16) return m->L == 32 ? launch_estep_L<32, PH, 0, 32, 4, true>(m, a, lds, grid, waves, nrep) : launch_estep_L<64, PH, 0, 32, 4, true>(m, a, lds, grid, waves, nrep);
-            if (m->L == 16) return launch_estep_L<16, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep);
-            if (m->L == 32) return launch_estep_L<32, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep);
-            return launch_estep_L<64, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep);
+            if (kmax > 32) return launch_estep_L<DL, 64, PH, 0, 64, 4, true>(m, a, lds, grid, waves, nrep, dl);
+            if (kmax > 16) return m->L == 32 ? launch_estep_L<DL, 32, PH, 0, 32, 4, true>(m, a, lds, grid, waves, nrep, dl) : launch_estep_L<DL, 64, PH, 0, 32, 4, true>(m, a, lds, grid, waves, nrep, dl);
+            if (m->L == 16) return launch_estep_L<DL, 16, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep, dl);
+            if (m->L == 32) return launch_estep_L<DL, 32, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep, dl);
+            return launch_estep_L<DL, 64, PH, 0, 16, 4, true>(m, a, lds, grid, waves, nrep, dl);
         }
-        if (kmax > 16) return m->L == 32 ? launch_estep_L<32, PH, 0, 32>(m, a, lds, grid, waves, nrep) : launch_estep_L<64, PH, 0, 32>(m, a, lds, grid, waves, nrep);
+        if (kmax > 16) return m->L == 32 ? launch_estep_L<DL, 32, PH, 0, 32>(m, a, lds, grid, waves, nrep, dl) : launch_estep_L<DL, 64, PH, 0, 32>(m, a, lds, grid, waves, nrep, dl);
         // the topic loops are unrolled to KMX: builds with KMX = 10 / 8 for the BASELINE shapes (K = [10,10,8], [10], [7,7]) instead of 16 --
         // the padded topics cost instructions (a product, two sums, a select and an exec-masked atomic each), not results
         const bool kfit = !mmm_off(m->tune, MMM_OFF_CTM_KFIT);
-        if (kfit && kmax <= 8 && m->L == 16) return launch_estep_L<16, PH, 0, 8>(m, a, lds, grid, waves, nrep);
-        if (kfit && kmax <= 10 && m->L == 16) return launch_estep_L<16, PH, 0, 10>(m, a, lds, grid, waves, nrep);
-        if (kfit && kmax <= 10 && m->L == 32) return launch_estep_L<32, PH, 0, 10>(m, a, lds, grid, waves, nrep);
+        if (kfit && kmax <= 8 && m->L == 16) return launch_estep_L<DL, 16, PH, 0, 8>(m, a, lds, grid, waves, nrep, dl);
+        if (kfit && kmax <= 10 && m->L == 16) return launch_estep_L<DL, 16, PH, 0, 10>(m, a, lds, grid, waves, nrep, dl);
+        if (kfit && kmax <= 10 && m->L == 32) return launch_estep_L<DL, 32, PH, 0, 10>(m, a, lds, grid, waves, nrep, dl);
     }
-    if (m->L == 16) return launch_estep_L<16, PH>(m, a, lds, grid, waves, nrep);
-    if (m->L == 32) return launch_estep_L<32, PH>(m, a, lds, grid, waves, nrep);
-    return launch_estep_L<64, PH>(m, a, lds, grid, waves, nrep);
+    if (m->L == 16) return launch_estep_L<DL, 16, PH>(m, a, lds, grid, waves, nrep, dl);
+    if (m->L == 32) return launch_estep_L<DL, 32, PH>(m, a, lds, grid, waves, nrep, dl);
+    return launch_estep_L<DL, 64, PH>(m, a, lds, grid, waves, nrep, dl);
 }
 
 // lam_in / expE: per-replica arrays (base of replica 0); lam_out likewise (may alias lam_in: in-place update)
@@ -295,17 +326,22 @@ struct StreamSwap {
     ~StreamSwap() { ctx->stream = saved; }
 };
 
-int run_estep(mmm_ctm* m, Scope sc, int flags, const double* lam_in, double* lam_out, const double* expE, double* lam_keep = nullptr,
-              double* expE_keep = nullptr, bool fork_after_theta = false)
+CtmEArgs estep_args(mmm_ctm* m, Scope sc, int flags, const double* lam_in, double* lam_out, const double* expE, double* lam_keep, double* expE_keep)
 {
     const CtmDims& dm = m->dm;
     const size_t r0 = sc.rep0, DMK = m->sDMK(), MK = dm.MK;
-    CtmEArgs a{m->dev(), m->invSigma.p + r0 * MK * MK, m->mu.p + r0 * MK, expE ? expE + r0 * dm.GT : nullptr, lam_in + r0 * DMK,
-               lam_out ? lam_out + r0 * DMK : nullptr, m->nu.p + r0 * DMK, m->zeta.p + r0 * dm.D * dm.M,
-               (flags & (F_THETA_STORED | F_THETA_STORE)) ? m->theta.p : nullptr, m->sumth.p + r0 * DMK,
-               m->wide ? nullptr : m->partial.p + r0 * m->grid_e * dm.GT, m->wide ? m->aexp.p + r0 * dm.D * MK : nullptr,
-               m->nev_nu.p + r0 * dm.D, m->nev_lam.p + r0 * dm.D, m->opt, flags, sc.active,
-               lam_keep ? lam_keep + r0 * DMK : nullptr, expE_keep ? expE_keep + r0 * dm.GT : nullptr};
+    return CtmEArgs{m->dev(), m->invSigma.p + r0 * MK * MK, m->mu.p + r0 * MK, expE ? expE + r0 * dm.GT : nullptr, lam_in + r0 * DMK,
+                    lam_out ? lam_out + r0 * DMK : nullptr, m->nu.p + r0 * DMK, m->zeta.p + r0 * dm.D * dm.M,
+                    (flags & (F_THETA_STORED | F_THETA_STORE)) ? m->theta.p : nullptr, m->sumth.p + r0 * DMK,
+                    m->wide ? nullptr : m->partial.p + r0 * m->grid_e * dm.GT, m->wide ? m->aexp.p + r0 * dm.D * MK : nullptr,
+                    m->nev_nu.p + r0 * dm.D, m->nev_lam.p + r0 * dm.D, m->opt, flags, sc.active,
+                    lam_keep ? lam_keep + r0 * DMK : nullptr, expE_keep ? expE_keep + r0 * dm.GT : nullptr};
+}
+
+int run_estep(mmm_ctm* m, Scope sc, int flags, const double* lam_in, double* lam_out, const double* expE, double* lam_keep = nullptr,
+              double* expE_keep = nullptr, bool fork_after_theta = false)
+{
+    CtmEArgs a = estep_args(m, sc, flags, lam_in, lam_out, expE, lam_keep, expE_keep);
     int rc;
     if (flags & (F_ZETA | F_THETA_COMPUTE | F_THETA_STORED | F_SLAB)) {
         const size_t lds = estep_lds(m, flags);
@@ -320,6 +356,29 @@ int run_estep(mmm_ctm* m, Scope sc, int flags, const double* lam_in, double* lam
         if (!mmm_off(m->tune, MMM_OFF_CTM_SOLVE_ORDER)) a.flags |= F_ORDER_LAM;      // the lambda solves' documents by the previous pass' evaluation counts (order_range)
         ProfSpan span(m->ctx);      // mmm_ctx_profile_*: event pair around the dominant kernel (the two LD_MMA solves)
         if ((rc = launch_phase<1>(m, a, solve_lds(m), m->grid_v, m->waves_s, sc.nrep))) return rc;
+    }
+    return MMM_OK;
+}
+
+// The stage kernels of run_estep on the n documents docs_dev[0..n) (device array, distinct ids) of the selected replica, in place: the
+// same builds, launch shapes (waves per block, LDS) and flags as the whole-corpus stage -- so a listed document gets exactly its
+// whole-corpus bits -- with the block counts sized from n (one block for one document).  Flags: any of F_ZETA, F_THETA_COMPUTE |
+// F_THETA_STORE, F_THETA_STORED (phase 0; not the fused pass's slabs), F_NU, F_LAMBDA (phase 1).
+int run_estep_docs(mmm_ctm* m, int flags, const double* expE, const int* docs_dev, int n)
+{
+    CtmEArgs a = estep_args(m, one(m), flags, m->lambda.p, (flags & F_LAMBDA) ? m->lambda.p : nullptr, expE, nullptr, nullptr);
+    const DocList dl{docs_dev, n};
+    int rc;
+    if (flags & (F_ZETA | F_THETA_COMPUTE | F_THETA_STORED)) {
+        const size_t lds = estep_lds(m, flags);
+        if (lds > 160 * 1024) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "CTM theta phase needs %zu B of LDS (> 160 KiB)", lds);
+        const int per_block = m->waves_e * (MMM_WAVE / m->L);
+        if ((rc = launch_phase<0, true>(m, a, lds, std::min(m->grid_e, (n + per_block - 1) / per_block), m->waves_e, 1, dl))) return rc;
+    }
+    if (flags & (F_NU | F_LAMBDA)) {
+        if (!mmm_off(m->tune, MMM_OFF_CTM_SOLVE_ORDER)) a.flags |= F_ORDER_LAM;
+        const int per_block = m->waves_s * (MMM_WAVE / m->Ls);
+        if ((rc = launch_phase<1, true>(m, a, solve_lds(m), std::min(m->grid_v, (n + per_block - 1) / per_block), m->waves_s, 1, dl))) return rc;
     }
     return MMM_OK;
 }
@@ -692,6 +751,7 @@ int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, c
     m->big = dm.MK > 64;      // more coordinates than lanes: the generic kernels of ctm_big.cuh (and the wide-table data flow)
     const int64_t nnz = doc_ptr[(size_t)(M - 1) * (D + 1) + D];
     m->nnz = nnz; m->theta_n = toff;
+    m->h_doc_ptr.assign(doc_ptr, doc_ptr + (size_t)M * (D + 1));
     // validate + pack the corpus
     std::vector<int2> tc((size_t)nnz);
     std::vector<double> Ndm((size_t)D * M, 0.0);
@@ -1237,49 +1297,122 @@ int mmm_ctm_doc_sums(mmm_ctm* m, int d, double* sumtheta, double* Ndivzeta)
     return MMM_OK;
 }
 
-// update_ζ!(model, d), update_θ!(model, d), update_ν!(model, d), update_λ!(model, d): the stage kernels process every document of the shard
-// in one launch, so the per-document form runs the stage and then puts every OTHER document's values back -- the field AND the solver's
-// per-document evaluation counters (only document d was logically solved) -- also when the stage fails.  Cost: O(D) per call (a D-sized
-// temporary and three device copies), i.e. the reference's `for d in 1:D update_ν!(model, d) end` costs O(D^2) here: the loop belongs to
-// mmm_ctm_update_nu(m), which is that loop as ONE launch; the per-document form exists for the reference's tests (test/mmctm.jl:92-199).
-int mmm_ctm_update_doc(mmm_ctm* m, int stage, int d)
+// update_ζ!(model, d), update_θ!(model, d), update_ν!(model, d), update_λ!(model, d) and fitdoc!(model, d) (MMCTM.jl:127-198, 450-455) on
+// a list of documents: the stage kernels' document-list builds (run_estep_docs), so a call costs the listed documents' work -- the
+// reference's `for d in 1:D fitdoc!(model, d) end` is O(D) in all.  A listed document gets, bit for bit, what the whole-corpus stage
+// writes for it; every other document keeps its values and counters.  The list is checked (ids in [0, D), no id twice) before
+// anything runs.
+int mmm_ctm_update_docs(mmm_ctm* m, int stage, const int32_t* docs, int n)
 {
     if (!m) return MMM_ERR_ARG;
     mmm_ctx* ctx = m->ctx;
-    int rc = begin_stage(m);
-    if (rc) return rc;
-    MMM_CHECK(ctx, d >= 0 && d < m->dm.D, "mmm_ctm_update_doc: document %d out of range", d);
-    MMM_CHECK(ctx, stage >= MMM_STAGE_ZETA && stage <= MMM_STAGE_LAMBDA, "mmm_ctm_update_doc: unknown stage %d", stage);
-    if (stage == MMM_STAGE_THETA && (rc = claim_theta(m))) return rc;
-    const int field = stage == MMM_STAGE_ZETA ? MMM_CTM_ZETA : stage == MMM_STAGE_THETA ? MMM_CTM_THETA : stage == MMM_STAGE_NU ? MMM_CTM_NU : MMM_CTM_LAMBDA;
-    double* p; size_t cnt;
-    if ((rc = ctm_field(m, field, &p, &cnt))) return rc;
-    const size_t D = (size_t)m->dm.D;
-    int* nev = stage == MMM_STAGE_NU ? m->nev_nu.p + (size_t)m->sel * D : (stage == MMM_STAGE_LAMBDA ? m->nev_lam.p + (size_t)m->sel * D : nullptr);
-    DevBuf<double> save;
-    DevBuf<int> save_nev;
-    MMM_HIP(ctx, save.alloc(cnt));
-    if (nev) MMM_HIP(ctx, save_nev.alloc(D));
-    if (cnt) MMM_HIP(ctx, hipMemcpyAsync(save.p, p, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
-    if (nev) MMM_HIP(ctx, hipMemcpyAsync(save_nev.p, nev, sizeof(int) * D, hipMemcpyDeviceToDevice, ctx->stream));
-    const int rc_stage = stage == MMM_STAGE_ZETA ? mmm_ctm_update_zeta(m) : stage == MMM_STAGE_THETA ? mmm_ctm_update_theta(m)
-                         : stage == MMM_STAGE_NU ? mmm_ctm_update_nu(m) : mmm_ctm_update_lambda(m);
-    // document d's new values into the saved copy (not after a failed stage: then everything goes back as it was), the saved copy back
-    if ((rc = ctm_field(m, field, &p, &cnt))) return rc;
-    if (!rc_stage) {
-        if (stage == MMM_STAGE_THETA) {
-            hipLaunchKernelGGL(k_ctm_copy_doc_theta, dim3(1), dim3(256), 0, ctx->stream, m->dev(), d, p, save.p);
-            MMM_LAUNCH_CHECK(ctx);
-        } else {
-            const size_t w = stage == MMM_STAGE_ZETA ? m->dm.M : m->dm.MK;
-            MMM_HIP(ctx, hipMemcpyAsync(save.p + (size_t)d * w, p + (size_t)d * w, sizeof(double) * w, hipMemcpyDeviceToDevice, ctx->stream));
+    MMM_CHECK(ctx, stage >= MMM_STAGE_ZETA && stage <= MMM_STAGE_FITDOC, "mmm_ctm_update_docs: unknown stage %d", stage);
+    MMM_CHECK(ctx, n >= 0, "mmm_ctm_update_docs: n = %d < 0", n);
+    MMM_CHECK(ctx, docs || n == 0, "mmm_ctm_update_docs: NULL document list");
+    {
+        // (two slots solving one document at once would race on its rows: a sorted copy finds repeats in O(n log n))
+        std::vector<int32_t> srt(docs, docs + n);
+        std::sort(srt.begin(), srt.end());
+        for (int i = 0; i < n; ++i) {
+            MMM_CHECK(ctx, srt[i] >= 0 && srt[i] < m->dm.D, "mmm_ctm_update_docs: document %d out of range (D = %d)", (int)srt[i], m->dm.D);
+            MMM_CHECK(ctx, i == 0 || srt[i] != srt[i - 1], "mmm_ctm_update_docs: document %d listed twice", (int)srt[i]);
         }
-        if (nev) MMM_HIP(ctx, hipMemcpyAsync(save_nev.p + d, nev + d, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (cnt) MMM_HIP(ctx, hipMemcpyAsync(p, save.p, sizeof(double) * cnt, hipMemcpyDeviceToDevice, ctx->stream));
-    if (nev) MMM_HIP(ctx, hipMemcpyAsync(nev, save_nev.p, sizeof(int) * D, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n == 0) return MMM_OK;
+    int rc = prep(m);
+    if (rc) return rc;
+    // theta of the unlisted documents must be the selected replica's before update_θ! overwrites the listed ones; update_λ! reads it
+    if (stage != MMM_STAGE_ZETA && stage != MMM_STAGE_NU && (rc = materialise_theta(m))) return rc;
+    if (m->doclist.n < (size_t)n) MMM_HIP(ctx, m->doclist.alloc(std::max((size_t)n, 2 * m->doclist.n)));
+    MMM_HIP(ctx, hipMemcpyAsync(m->doclist.p, docs, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    const int* dl = m->doclist.p;
+    switch (stage) {
+        case MMM_STAGE_ZETA: rc = run_estep_docs(m, F_ZETA, nullptr, dl, n); break;
+        case MMM_STAGE_THETA: rc = run_estep_docs(m, F_THETA_COMPUTE | F_THETA_STORE, m->expEeff.p, dl, n); break;
+        case MMM_STAGE_NU: rc = run_estep_docs(m, F_NU, nullptr, dl, n); break;
+        case MMM_STAGE_LAMBDA: rc = run_estep_docs(m, F_THETA_STORED | F_LAMBDA, nullptr, dl, n); break;
+        default:
+            // fitdoc!: ζ and θ in one theta-phase launch (θ does not read ζ), then what update_ν! and update_λ! launch -- sumθ from the stored
+            // θ, the ν solves, the λ solves with the new ν -- with the two solves in one launch, as the fused pass runs them: same bits as the
+            // four stage calls one after the other
+            rc = run_estep_docs(m, F_ZETA | F_THETA_COMPUTE | F_THETA_STORE, m->expEeff.p, dl, n);
+            if (!rc) rc = run_estep_docs(m, F_THETA_STORED | F_NU | F_LAMBDA, nullptr, dl, n);
+            break;
+    }
+    if (!rc && (stage == MMM_STAGE_THETA || stage == MMM_STAGE_FITDOC)) m->theta_state[m->sel] = 2;      // (theta_rep == sel: materialised above)
+    if (rc) return rc;
     MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return rc_stage;
+    return MMM_OK;
+}
+
+int mmm_ctm_update_doc(mmm_ctm* m, int stage, int d)
+{
+    const int32_t one_doc = d;
+    return mmm_ctm_update_docs(m, stage, &one_doc, 1);
+}
+
+// document d's part of a per-document field of the selected replica: up to M contiguous device spans (theta: one per modality)
+struct DocSpans { double* p[kMaxM]; size_t n[kMaxM]; int count; size_t total; };
+
+static int doc_spans(mmm_ctm* m, int field, int d, DocSpans& sp)
+{
+    MMM_CHECK(m->ctx, d >= 0 && d < m->dm.D, "document %d out of range (D = %d)", d, m->dm.D);
+    const size_t MK = m->dm.MK, M = m->dm.M, D = m->dm.D, r = m->sel;
+    sp.count = 1;
+    switch (field) {
+        case MMM_CTM_LAMBDA: sp.p[0] = m->lambda.p + (r * D + d) * MK; sp.n[0] = MK; break;
+        case MMM_CTM_NU: sp.p[0] = m->nu.p + (r * D + d) * MK; sp.n[0] = MK; break;
+        case MMM_CTM_PROPS: sp.p[0] = m->props.p + (r * D + d) * MK; sp.n[0] = MK; break;
+        case MMM_CTM_ZETA: sp.p[0] = m->zeta.p + (r * D + d) * M; sp.n[0] = M; break;
+        case MMM_CTM_THETA:       // the flat layout: modality m's entries e of document d at toff[m] + (e - estart[m]) K_m
+            sp.count = (int)M;
+            for (size_t i = 0; i < M; ++i) {
+                const int64_t e0 = m->h_doc_ptr[i * (D + 1) + d], e1 = m->h_doc_ptr[i * (D + 1) + d + 1];
+                sp.p[i] = m->theta.p + m->dm.toff[i] + (size_t)(e0 - m->dm.estart[i]) * m->dm.K[i];
+                sp.n[i] = (size_t)(e1 - e0) * m->dm.K[i];
+            }
+            break;
+        default: return mmm_fail(m->ctx, MMM_ERR_ARG, "CTM field %d has no per-document part", field);
+    }
+    sp.total = 0;
+    for (int i = 0; i < sp.count; ++i) sp.total += sp.n[i];
+    return MMM_OK;
+}
+
+int mmm_ctm_get_doc(mmm_ctm* m, int field, int d, double* host, size_t n)
+{
+    if (!m) return MMM_ERR_ARG;
+    mmm_ctx* ctx = m->ctx;
+    int rc = prep(m);
+    if (rc) return rc;
+    DocSpans sp;
+    if ((rc = doc_spans(m, field, d, sp))) return rc;
+    MMM_CHECK(ctx, (host || n == 0) && n == sp.total, "mmm_ctm_get_doc(field %d, document %d): expected %zu doubles, got %zu", field, d, sp.total, n);
+    if (field == MMM_CTM_THETA && (rc = materialise_theta(m))) return rc;
+    size_t o = 0;
+    for (int i = 0; i < sp.count; o += sp.n[i], ++i)
+        if (sp.n[i]) MMM_HIP(ctx, hipMemcpyAsync(host + o, sp.p[i], sizeof(double) * sp.n[i], hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MMM_OK;
+}
+
+int mmm_ctm_set_doc(mmm_ctm* m, int field, int d, const double* host, size_t n)
+{
+    if (!m) return MMM_ERR_ARG;
+    mmm_ctx* ctx = m->ctx;
+    int rc = prep(m);
+    if (rc) return rc;
+    DocSpans sp;
+    if ((rc = doc_spans(m, field, d, sp))) return rc;
+    MMM_CHECK(ctx, (host || n == 0) && n == sp.total, "mmm_ctm_set_doc(field %d, document %d): expected %zu doubles, got %zu", field, d, sp.total, n);
+    // theta: the other documents' values must be the selected replica's (also when it was held implicitly) -- then it is explicit
+    if (field == MMM_CTM_THETA && (rc = materialise_theta(m))) return rc;
+    size_t o = 0;
+    for (int i = 0; i < sp.count; o += sp.n[i], ++i)
+        if (sp.n[i]) MMM_HIP(ctx, hipMemcpyAsync(sp.p[i], host + o, sizeof(double) * sp.n[i], hipMemcpyHostToDevice, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (field == MMM_CTM_THETA) m->theta_state[m->sel] = 2;
+    return MMM_OK;
 }
 
 int mmm_ctm_solver_stats(mmm_ctm* m, int64_t* n_eval_nu, int64_t* n_eval_lambda, int64_t* n_capped, int* per_doc_nu, int* per_doc_lambda)

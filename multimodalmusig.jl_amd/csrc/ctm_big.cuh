@@ -20,8 +20,12 @@ constexpr int kBigSlots = 4;          // coordinates per lane in the coupled pie
 
 // ---- theta phase (PH = 0 of k_ctm_estep, wide-table flavour): zeta, theta, sum theta, a_k rows for the posting sweep ---------------
 // grid (blocks, replicas), 256 threads; dynamic LDS per wave: [64] a_k of the current modality | [64][64] column sums
-__global__ __launch_bounds__(256) void k_ctm_theta_big(CtmEArgs a)
+// DLA = DocList (ctm_estep.cuh): a wave's positions index the document list
+template <class... DLA>
+__global__ __launch_bounds__(256) void k_ctm_theta_big(CtmEArgs a, DLA... dla)
 {
+    constexpr bool DL = sizeof...(DLA) > 0;
+    const DocList dl = doc_list(dla...);
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const CtmDims& dm = a.c.dm;
     const int MK = dm.MK, M = dm.M, D = dm.D, GT = dm.GT;
@@ -36,7 +40,9 @@ __global__ __launch_bounds__(256) void k_ctm_theta_big(CtmEArgs a)
     double* wav = smem + (size_t)wid * (64 + 64 * 64);
     double* wacc = wav + 64;
     const int flags = a.flags;
-    for (int d = blockIdx.x * NW + wid; d < D; d += gridDim.x * NW) {
+    const int NP = DL ? dl.n : D;
+    for (int p = blockIdx.x * NW + wid; p < NP; p += gridDim.x * NW) {
+        const int d = DL ? dl.docs[p] : p;
         for (int m = 0; m < M; ++m) {
             const int Km = dm.K[m], Vm = dm.V[m], off = dm.koff[m];
             const bool act = lane < Km;
@@ -235,9 +241,12 @@ __device__ int mma_big(const Obj& obj, const BigDoc& dc, double (&x)[kBigSlots],
     }
 }
 
-// grid (blocks, replicas), 256 threads; dynamic LDS: [waves][MK] difference vectors
-__global__ __launch_bounds__(256) void k_ctm_solve_big(CtmEArgs a)
+// grid (blocks, replicas), 256 threads; dynamic LDS: [waves][MK] difference vectors; DLA as in k_ctm_theta_big
+template <class... DLA>
+__global__ __launch_bounds__(256) void k_ctm_solve_big(CtmEArgs a, DLA... dla)
 {
+    constexpr bool DL = sizeof...(DLA) > 0;
+    const DocList dl = doc_list(dla...);
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const CtmDims& dm = a.c.dm;
     const int MK = dm.MK, M = dm.M, D = dm.D;
@@ -268,7 +277,9 @@ __global__ __launch_bounds__(256) void k_ctm_solve_big(CtmEArgs a)
         Sll[q] = i < MK ? S[(size_t)i * MK + i] : 0.0;
     }
     const SolveOpts o = a.opt;
-    for (int d = blockIdx.x * NW + wid; d < D; d += gridDim.x * NW) {
+    const int NP = DL ? dl.n : D;
+    for (int p = blockIdx.x * NW + wid; p < NP; p += gridDim.x * NW) {
+        const int d = DL ? dl.docs[p] : p;
         BigDoc dc;
         double lam[kBigSlots], nu[kBigSlots], sumth[kBigSlots];
 #pragma unroll

@@ -282,6 +282,19 @@ struct CtmEArgs {
     double* lam_keep; double* expE_keep;
 };
 
+// Document-list builds of the stage kernels (mmm_ctm_update_docs): the list is a SECOND kernel argument, present only there -- the kernels
+// end in a parameter pack `DLA...` that is empty for the whole-corpus builds (whose argument block, and so whose code, stays as it was) and
+// one DocList for the list builds.  Work position p < n is document docs[p] (distinct ids of the shard).
+struct DocList { const int* docs; int n; };
+
+template <class... T>
+__device__ __forceinline__ DocList doc_list(const T&... t)
+{
+    DocList r{nullptr, 0};
+    ((r = t), ...);
+    return r;
+}
+
 // PH = 0: zeta / theta / sumtheta / gamma slabs (register-heavy, table- and slab-staged);
 // PH = 1: the two LD_MMA solves (few registers, high occupancy: the solves are latency-bound dependent chains)
 // OCC (solve phase): 4 waves per SIMD -- 128 VGPRs, with a few spilled values for MK = 10 / 14 -- when the launch has the waves to
@@ -290,9 +303,13 @@ struct CtmEArgs {
 // the gamma statistics come from k_ctm_stats_terms, a term-major sweep over posting lists that evaluates theta_kw again from
 // the exp(lambda - max) rows this phase leaves in `aexp` (the scheme of the LDA wide path, lda.hip)
 // PACK (solve phase, MKT = sum K with 64 % MKT != 0): MKT lanes per document instead of L (packed_sum above)
-template <int L, int PH, int MKT = 0, int KMX = 16, int OCC = 4, bool WIDE = false, bool PACK = false>
-__global__ __launch_bounds__(PH ? 256 : 512, PH ? OCC : 1) void k_ctm_estep(CtmEArgs a)
+// DLA = DocList (stage calls on a document list): the groups walk the positions 0..n-1 of the list instead of the documents 0..D-1; a
+// document's group does exactly what it does in the whole-corpus build (no fused-pass slabs in this build)
+template <int L, int PH, int MKT = 0, int KMX = 16, int OCC = 4, bool WIDE = false, bool PACK = false, class... DLA>
+__global__ __launch_bounds__(PH ? 256 : 512, PH ? OCC : 1) void k_ctm_estep(CtmEArgs a, DLA... dla)
 {
+    constexpr bool DL = sizeof...(DLA) > 0;
+    const DocList dl = doc_list(dla...);
     extern __shared__ __attribute__((aligned(16))) double smem[];
     static_assert(!PACK || (PH == 1 && MKT > 0 && MMM_WAVE % MKT != 0), "packed groups: solve phase with compile-time sum K");
     constexpr int LG = PACK ? MKT : L;          // lanes per document group
@@ -349,7 +366,7 @@ __global__ __launch_bounds__(PH ? 256 : 512, PH ? OCC : 1) void k_ctm_estep(CtmE
     // (max_m K_m V_m doubles instead of sum_m K_m V_m: config 4 115 -> 76 KB of LDS per block, two blocks per CU instead of one); the
     // block sweeps its documents once per modality and flushes the slabs in between.  Every statistic receives its addends in the
     // same order as in a document-major sweep (documents in step order, lanes ascending), so the sums keep their bits.
-    if constexpr (PH == 0 && !WIDE) {
+    if constexpr (PH == 0 && !WIDE && !DL) {
         if (flags & F_SLAB) {
             int slabn = 0;
             for (int m = 0; m < M; ++m) slabn = max(slabn, dm.K[m] * dm.V[m]);
@@ -446,9 +463,11 @@ __global__ __launch_bounds__(PH ? 256 : 512, PH ? OCC : 1) void k_ctm_estep(CtmE
     int mod_l = 0;
     for (int m = 0; m < M; ++m) if (l >= dm.koff[m] && l < dm.koff[m + 1]) mod_l = m;
 
-    for (int base = (blockIdx.x * NW + wid) * G; base < D; base += gridDim.x * NW * G) {
-        const int d = base + g;
-        const bool valid = ingrp && d < D;
+    const int NP = DL ? dl.n : D;      // work positions
+    for (int base = (blockIdx.x * NW + wid) * G; base < NP; base += gridDim.x * NW * G) {
+        const int p = base + g;
+        const bool valid = ingrp && p < NP;
+        const int d = DL ? (valid ? dl.docs[p] : 0) : p;
         const bool act = valid && l < MK;
         double lam = act ? p_lam_in[(size_t)d * MK + l] : 0.0;
         double nu = act ? p_nu[(size_t)d * MK + l] : 1.0;
@@ -896,9 +915,11 @@ struct LamObjC {
 // In lock step a wave runs to its last solve with the other slots idle; the long solves started first leave the short ones for the end
 // (the counts of consecutive passes correlate at 0.5-0.7 for the lambda solves of config 5, not at all for the nu solves:
 // tools/sim_solve_schedule.py).  A document's solve does not depend on its slot or its neighbours: not a bit changes.  n <= 64.
-__device__ __forceinline__ void order_range(const int* prev, int r0, int n, int lane, int* s_perm)
+// (DL: the range is one of positions in `docs`)
+template <bool DL>
+__device__ __forceinline__ void order_range(const int* prev, const int* docs, int r0, int n, int lane, int* s_perm)
 {
-    const int pv = lane < n ? prev[r0 + lane] : 0;
+    const int pv = lane < n ? prev[DL ? docs[r0 + lane] : r0 + lane] : 0;
     const int key = lane < n ? ((pv < 0 ? -pv : pv) & (MMM_NEV_NONFINITE - 1)) : -1;
     int rank = 0;
     for (int j = 0; j < n; ++j) {
@@ -910,16 +931,21 @@ __device__ __forceinline__ void order_range(const int* prev, int r0, int n, int 
     lds_wave_sync();
 }
 
-template <int MKT, int LPD, bool SB, class Obj>
-__device__ __forceinline__ void solve_range(Obj& obj, const CplDocs& dc, int r0, int r1, int lane, bool has_lb, double lb, const SolveOpts& o, int* nev_out,
-                                            bool by_count, int* s_perm)
+// DL: [r0, r1) are positions in `docs`, position p solves document docs[p]
+template <int MKT, int LPD, bool SB, bool DL, class Obj>
+__device__ __forceinline__ void solve_range(Obj& obj, const CplDocs& dc, const int* docs, int r0, int r1, int lane, bool has_lb, double lb, const SolveOpts& o,
+                                            int* nev_out, bool by_count, int* s_perm)
 {
     constexpr int CPL = CplGeom<MKT, LPD>::CPL, G = MMM_WAVE / LPD;
     const int g = lane / LPD, l = lane % LPD;
     const int n = r1 - r0;
     const bool ord = by_count && nev_out != nullptr && n > G && n <= MMM_WAVE;      // (n <= G: every document has a slot at once)
-    if (ord) order_range(nev_out, r0, n, lane, s_perm);
-    auto doc_at = [&](int p) { return r0 + (ord ? s_perm[p < n ? p : 0] : p); };
+    if (ord) order_range<DL>(nev_out, docs, r0, n, lane, s_perm);
+    auto doc_at = [&](int p) {
+        const int q = r0 + (ord ? s_perm[p < n ? p : 0] : p);
+        if constexpr (DL) return p < n ? docs[q] : 0;      // (p >= n: no document, the slot goes idle)
+        else return q;
+    };
     int next = G;
     bool have = g < n, fresh = true;
     int d = doc_at(g);
@@ -1034,9 +1060,12 @@ __device__ __forceinline__ void solve_range(Obj& obj, const CplDocs& dc, int r0,
     }
 }
 
-template <int MKT, int LPD, int OCC, bool SB>
-__global__ __launch_bounds__(256, OCC) void k_ctm_solve_cpl(CtmEArgs a)
+// DLA = DocList: the waves' contiguous ranges are ranges of positions in the list (document-list stage calls)
+template <int MKT, int LPD, int OCC, bool SB, class... DLA>
+__global__ __launch_bounds__(256, OCC) void k_ctm_solve_cpl(CtmEArgs a, DLA... dla)
 {
+    constexpr bool DL = sizeof...(DLA) > 0;
+    const DocList dl = doc_list(dla...);
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using Gm = CplGeom<MKT, LPD>;
     constexpr int CPL = Gm::CPL, G = Gm::G, MK = MKT;
@@ -1072,7 +1101,8 @@ __global__ __launch_bounds__(256, OCC) void k_ctm_solve_cpl(CtmEArgs a)
     // (balanced: the first D % nwaves waves take one document more -- with ceil(D / nwaves) per wave a launch of one wave per SIMD over a small
     // shard left its last waves without documents)
     const int nwaves = gridDim.x * NW, w = blockIdx.x * NW + wid;
-    const int base = D / nwaves, rem = D % nwaves;
+    const int NP = DL ? dl.n : D;
+    const int base = NP / nwaves, rem = NP % nwaves;
     const int r0 = w * base + min(w, rem), r1 = r0 + base + (w < rem ? 1 : 0);
     static_assert(CPL <= 7, "modality indices are packed 4 bits each into one int");
     int modpack = 0;
@@ -1095,7 +1125,7 @@ __global__ __launch_bounds__(256, OCC) void k_ctm_solve_cpl(CtmEArgs a)
         for (int q = 0; q < CPL; ++q) obj.Sll[q] = lane_on ? p_invSigma[(size_t)(l * CPL + q) * MK + l * CPL + q] : 0.0;
         obj.modpack = modpack; obj.uni = uni;
         obj.l = l; obj.lane_on = lane_on; obj.tabs = sTabs;
-        solve_range<MKT, LPD, SB>(obj, dc, r0, r1, lane, true, o.nu_lower, o, p_nev_nu, false, sPerm[wid]);      // (the nu solves' counts of consecutive passes do not correlate)
+        solve_range<MKT, LPD, SB, DL>(obj, dc, dl.docs, r0, r1, lane, true, o.nu_lower, o, p_nev_nu, false, sPerm[wid]);      // (the nu solves' counts of consecutive passes do not correlate)
     }
     // the λ solves read the ν this wave has just stored (any slot may have solved a given document's ν)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1107,6 +1137,6 @@ __global__ __launch_bounds__(256, OCC) void k_ctm_solve_cpl(CtmEArgs a)
         obj.tabs = sTabs;
         obj.smu = sMu;
         obj.l = l; obj.lane_on = lane_on; obj.sS = sS; obj.scr = sScr + ((size_t)wid * G + g) * (MK + 2);
-        solve_range<MKT, LPD, SB>(obj, dc, r0, r1, lane, false, 0.0, o, p_nev_lam, (a.flags & F_ORDER_LAM) != 0, sPerm[wid]);
+        solve_range<MKT, LPD, SB, DL>(obj, dc, dl.docs, r0, r1, lane, false, 0.0, o, p_nev_lam, (a.flags & F_ORDER_LAM) != 0, sPerm[wid]);
     }
 }

@@ -51,17 +51,6 @@ __global__ __launch_bounds__(256) void k_ctm_doc_sums(CtmDev c, int d, const dou
     out[MK + l] = c.Ndm[(size_t)d * M + m] / zeta[(size_t)d * M + m];
 }
 
-// dst's theta columns of document d <- src's (per-document stage calls: only document d keeps the stage's result)
-__global__ __launch_bounds__(256) void k_ctm_copy_doc_theta(CtmDev c, int d, const double* src, double* dst)
-{
-    const CtmDims& dm = c.dm;
-    for (int m = 0; m < dm.M; ++m) {
-        const int64_t* dp = c.doc_ptr + (size_t)m * (dm.D + 1);
-        const size_t b = dm.toff[m] + (size_t)(dp[d] - dm.estart[m]) * dm.K[m], n = (size_t)(dp[d + 1] - dp[d]) * dm.K[m];
-        for (size_t i = threadIdx.x; i < n; i += blockDim.x) dst[b + i] = src[b + i];
-    }
-}
-
 // wide tables: gamma statistics of one (modality, term) per block -- sums[goff[m] + k V_m + v] = sum over the term's postings of
 // n theta_kw (MMCTM.jl:230-240), theta_kw = a_dk e_kv / sum_k' a_dk' e_k'v from the theta phase's a_d rows and the term's table
 // column (scalar registers).  Postings (doc, count) in document order, split over the block's waves in contiguous segments,

@@ -1,9 +1,10 @@
 """Host-side mirror of `MMCTM` (src/MMCTM.jl) and `IMMCTM` (src/IMMCTM.jl) over the HIP backend.
 
 Field names follow the reference structs (MMCTM.jl:1-27, IMMCTM.jl:1-27).  State lives in HBM inside the C-ABI handle;
-nested fields (`model.θ[d][m]`, `model.γ[m][k]`, ...) are write-through views.  The per-document functions of the
-reference (`update_ζ!(model, d)`, ...) change document d only (0-based here; mmm_ctm_update_doc); without `d` they process
-every document in one launch, which is what `fitdoc!` over all documents does.  The reference's free functions (λ_objective,
+nested fields (`model.θ[d][m]`, `model.γ[m][k]`, ...) are write-through views; a per-document leaf (`model.λ[d]`, `model.θ[d][m]`,
+...) moves only that document's values.  The per-document functions of the reference (`update_ζ!(model, d)`, ..., `fitdoc!(model, d)`)
+change document d only (0-based here), or every document of a sequence `d` in one set of launches (mmm_ctm_update_docs); without `d`
+they process every document, which is what `fitdoc!` over all documents does.  The reference's free functions (λ_objective,
 ν_objective, α_objective, calculate_modality_loglikelihood: common.jl:11-46, MMCTM.jl:384-418, IMMCTM.jl:362-407) are
 here as functions over plain arrays.  There is no CPU implementation in this package.
 """
@@ -170,9 +171,48 @@ class _CTM:
             return self._topic_span(name, path)
         raise KeyError(name)
 
+    # per-document fields: document d's part travels alone (mmm_ctm_get_doc / mmm_ctm_set_doc), not the whole field
+    _DOC_FIELDS = ("lambda", "nu", "zeta", "props", "theta")
+
+    def _doc_size(self, name, d):
+        if name == "zeta":
+            return self.M
+        if name == "theta":
+            return int(sum(self.K[m] * self._doc_w(d, m) for m in range(self.M)))
+        return self.MK
+
+    def _doc_w(self, d, m):
+        D = self.D
+        return int(self._doc_ptr[m * (D + 1) + d + 1]) - int(self._doc_ptr[m * (D + 1) + d])
+
+    def _get_doc(self, name, d):
+        out = np.empty(self._doc_size(name, d), dtype=np.float64)
+        check(lib().mmm_ctm_get_doc(self._h, _FID[name], int(d), out, out.size), self.ctx.h, "mmm_ctm_get_doc(%s, %d)" % (name, d))
+        return out
+
+    def _set_doc(self, name, d, flat):
+        flat = np.ascontiguousarray(flat, dtype=np.float64)
+        check(lib().mmm_ctm_set_doc(self._h, _FID[name], int(d), flat, flat.size), self.ctx.h, "mmm_ctm_set_doc(%s, %d)" % (name, d))
+
+    def _doc_leaf(self, name, path):
+        """(start, stop, shape-for-reshape, transpose?) of a leaf inside its document's part (mmm_ctm_get_doc layout)."""
+        d = path[0]
+        if name in ("lambda", "nu", "zeta"):
+            return 0, self._doc_size(name, d), None, False
+        m = path[1]
+        if name == "props":
+            return int(self._koff[m]), int(self._koff[m + 1]), None, False
+        a = int(sum(self.K[q] * self._doc_w(d, q) for q in range(m)))          # theta: modality-major blocks of K_q x W_dq
+        W = self._doc_w(d, m)
+        return a, a + self.K[m] * W, (W, self.K[m]), True
+
     def _leaf_get(self, name, path):
-        a, b, shape, tr = self._span(name, path)
-        v = self._get(name)[a:b].copy()
+        if name in self._DOC_FIELDS:
+            a, b, shape, tr = self._doc_leaf(name, path)
+            v = self._get_doc(name, path[0])[a:b].copy()
+        else:
+            a, b, shape, tr = self._span(name, path)
+            v = self._get(name)[a:b].copy()
         if shape is not None:
             v = v.reshape(shape)
             if tr:
@@ -180,13 +220,20 @@ class _CTM:
         return v
 
     def _leaf_set(self, name, path, value):
-        a, b, shape, tr = self._span(name, path)
+        doc = name in self._DOC_FIELDS
+        a, b, shape, tr = self._doc_leaf(name, path) if doc else self._span(name, path)
         value = np.asarray(value, dtype=np.float64)
         if tr:
             value = value.T
-        flat = self._get(name)
         if value.size != b - a:
             raise ValueError("%s%s expects %d values, got %d" % (name, list(path), b - a, value.size))
+        if doc:
+            full = b - a == self._doc_size(name, path[0])
+            flat = np.empty(b - a) if full else self._get_doc(name, path[0])
+            flat[a:b] = value.ravel()
+            self._set_doc(name, path[0], flat)
+            return
+        flat = self._get(name)
         flat[a:b] = value.ravel()
         self._set(name, flat)
 
@@ -368,11 +415,21 @@ def _call(model, fn, what):
     check(getattr(lib(), fn)(model._h), model.ctx.h, what)
 
 
+def _doc_list(d):
+    """d: one document id or a sequence of them -> contiguous int32 array (ids are checked by the library)"""
+    a = np.atleast_1d(np.asarray(d, dtype=np.int64)).ravel()
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("document id out of range")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def _doc_stage(model, fn, stage, what, d):
     if d is None:
         _call(model, fn, what)
     else:
-        check(lib().mmm_ctm_update_doc(model._h, stage, int(d)), model.ctx.h, "%s(model, %d)" % (what, d))
+        docs = _doc_list(d)
+        check(lib().mmm_ctm_update_docs(model._h, stage, docs.ctypes.data if docs.size else None, int(docs.size)), model.ctx.h,
+              "%s(model, %s)" % (what, d if np.ndim(d) == 0 else "[%d documents]" % docs.size))
 
 
 def update_ζ(model, d=None):      # MMCTM.jl:172-181
@@ -506,7 +563,11 @@ def update_ϕ_ctm(model):          # MMCTM.jl:244-250
 
 
 def fitdoc(model, d=None):        # MMCTM.jl:450-455
-    update_ζ(model); update_θ_ctm(model); update_ν(model); update_λ_ctm(model)
+    """fitdoc!(model, d): ζ, θ, ν, λ of document d -- or of every document of a sequence d, in one set of launches; without d every document"""
+    if d is None:
+        update_ζ(model); update_θ_ctm(model); update_ν(model); update_λ_ctm(model)
+    else:
+        _doc_stage(model, None, 4, "fitdoc!", d)       # MMM_STAGE_FITDOC
 
 
 def calculate_loglikelihoods(model):   # MMCTM.jl:446-448 / IMMCTM.jl:408-428

@@ -409,6 +409,35 @@ int mmm_mixture_loglik(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr
 int mmm_mixture_loglik_features(mmm_ctx* ctx, int D, int K, int V, int I, const int* J, const int32_t* features, const int64_t* doc_ptr,
                                 const int32_t* term, const int32_t* count, const double* eta, int softmax, const double* phi, double* ll);
 
+/* ---- bootstrap of the exposures under trained topics (no counterpart in the reference; DESIGN.md "Bootstrap of the exposures") -------------
+ * Resample every sample's counts multinomially B times, infer the exposures of every replicate under the frozen topics (the stacked
+ * corpus of B x D replicate documents goes through the existing frozen-topic passes: mmm_lda_infer / mmm_ctm_infer), summarise.  The two
+ * entry points below are the pieces around those passes; they take caller arrays, need no model and no communicator (on a multi-rank
+ * context they act on the arrays they are given: no collective). */
+/* B multinomial resamples of every document of a CSR corpus, drawn on the GPU.
+ * out[b * nnz + e], b = 0..B-1: the resampled count of entry e in replicate b0 + b.
+ * The sparsity pattern is kept: an entry may come out 0; a document keeps its total N_d.
+ * Random numbers: Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9, 0xBB67AE85), key =
+ * (seed low 32 bits, seed high 32 bits), counter = (i / 4, d, b, stream) with d the document index in the arrays given, b the GLOBAL
+ * replicate index (b0 + ..., so chunked calls are slices of one big call) and i the draw index within the (document, replicate) pair; draw
+ * i is output word i % 4 of its block.  Draw: for the 32-bit word u and the document total N_d, r = (uint64(u) * N_d) >> 32 (all integer;
+ * bias <= N_d / 2^32, not corrected); with cum the inclusive prefix sums of the document's counts in CSR order the draw lands in the
+ * entry e with cum[e-1] <= r < cum[e].  A zero count never receives a draw; N_d = 0 gives an all-zero row.  Output = draws per entry.
+ * The same arguments give the same bits on every run.
+ * MMM_ERR_ARG: NULL pointer, negative count, doc_ptr[0] != 0 or decreasing doc_ptr, B < 0, b0 < 0, b0 + B > 2^31 - 1;
+ * MMM_ERR_UNSUPPORTED: some N_d >= 2^31.  B = 0 or nnz = 0: MMM_OK, nothing written. */
+int mmm_resample_counts(mmm_ctx* ctx, int D, const int64_t* doc_ptr, const int32_t* count, int B, int b0, uint64_t seed, uint32_t stream,
+                        int32_t* out);
+/* x[b * n + j], b < B: B replicates of n values.  Per column j, with x_(0) <= ... <= x_(B-1) its sorted values:
+ *   mean[j] = (sum_b x_b) / B, summed in replicate order;
+ *   sd[j] = sqrt(sum_b (x_b - mean)^2 / (B - 1)) (two passes, Julia's std; 0 when B = 1);
+ *   quant[i * n + j] = the q[i]-quantile (0 <= q[i] <= 1, i < nq): h = (B - 1) q, lo = floor(h),
+ *                      x_(lo) + (h - lo) (x_(min(lo + 1, B - 1)) - x_(lo)) -- Julia's default quantile, numpy's "linear";
+ *                      q = 0 and q = 1 are the minimum and the maximum exactly.
+ * Any of mean / sd / quant may be NULL.  A column that contains a NaN gives NaN in all its outputs.  1 <= B <= 4096 (a column is sorted
+ * in LDS); MMM_ERR_UNSUPPORTED above that; MMM_ERR_ARG for B < 1, a q outside [0, 1], NULL x or q. */
+int mmm_replicate_summary(mmm_ctx* ctx, int B, size_t n, const double* x, int nq, const double* q, double* mean, double* sd, double* quant);
+
 #ifdef __cplusplus
 }
 #endif

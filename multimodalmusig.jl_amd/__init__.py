@@ -12,8 +12,10 @@ from .ctm import (calculate_docmodality_loglikelihood, calculate_modality_loglik
                   update_ν)
 from .inference import fit_heldout, predict_modality_η, transform
 from .restarts import fit_lda_restarts
-from .utils import (format_counts_ctm, format_counts_lda, format_counts_mmctm, make_count_matrix, pack_lda,
+from .bootstrap import BootstrapResult, bootstrap_exposures, replicate_summary, resample_counts
+from .utils import (PackedCorpus, format_counts_ctm, format_counts_lda, format_counts_mmctm, make_count_matrix, pack_lda,
                     pack_mm, read_counts_tsv, shard_documents)
 
 __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_lda", "format_counts_ctm", "format_counts_mmctm", "Context",
-           "MmmError", "build", "fit_restarts", "fit_lda_restarts", "transform", "fit_heldout", "predict_modality_η"]
+           "MmmError", "build", "fit_restarts", "fit_lda_restarts", "transform", "fit_heldout", "predict_modality_η",
+           "bootstrap_exposures", "resample_counts", "replicate_summary", "BootstrapResult", "PackedCorpus"]

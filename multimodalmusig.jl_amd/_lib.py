@@ -131,6 +131,8 @@ _SIGS = {
     "mmm_alpha_objective": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mmm_mixture_loglik": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, f64p, C.POINTER(C.c_double)]),
     "mmm_mixture_loglik_features": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i64p, vp, vp, f64p, C.c_int, f64p, C.POINTER(C.c_double)]),
+    "mmm_resample_counts": (C.c_int, [vp, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]),
+    "mmm_replicate_summary": (C.c_int, [vp, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, vp]),
 }
 
 

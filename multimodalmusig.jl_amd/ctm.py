@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SolverOpts, check, lib
-from .utils import pack_mm
+from .utils import doc_totals, pack_mm
 
 _FID = {"mu": 0, "Sigma": 1, "invSigma": 2, "gamma": 3, "Elnphi": 4, "phi": 5, "lambda": 6, "nu": 7, "zeta": 8,
         "props": 9, "theta": 10, "alpha": 11}
@@ -68,8 +68,7 @@ class _CTM:
         self.D = len(X)
         self._doc_ptr, self._term, self._count = pack_mm(X, self.M)
         D = self.D
-        self.N = [[int(self._count[self._doc_ptr[m * (D + 1) + d]:self._doc_ptr[m * (D + 1) + d + 1]].sum()) for m in range(self.M)]
-                  for d in range(D)]
+        self.N = np.concatenate([doc_totals(self._doc_ptr, self._count), [0]]).reshape(self.M, D + 1)[:, :D].T.tolist() if D else []
         self._estart = [int(self._doc_ptr[m * (D + 1)]) for m in range(self.M)]
         self._nnz = [int(self._doc_ptr[m * (D + 1) + D]) - self._estart[m] for m in range(self.M)]
         self._toff = np.concatenate([[0], np.cumsum([self._nnz[m] * self.K[m] for m in range(self.M)])]).astype(np.int64)

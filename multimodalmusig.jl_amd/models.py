@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MmmError, check, lib
-from .utils import pack_lda, pack_mm
+from .utils import doc_totals, pack_lda, pack_mm
 
 # field ids of include/mmmusig.h (ASCII keys: Python NFKC-normalises identifiers, so `ϕ` typed as a keyword
 # would not equal the string "ϕ")
@@ -63,7 +63,7 @@ class LDA:
         if V is None:
             V = int(self._term.max()) + 1 if self._term.size else 0     # LDA.jl:57-66
         self.V = int(V)
-        self.N = np.array([int(self._count[self._doc_ptr[d]:self._doc_ptr[d + 1]].sum()) for d in range(self.D)], dtype=np.int64)
+        self.N = doc_totals(self._doc_ptr, self._count)
         def draw(sd):
             return np.random.default_rng(sd).integers(1, 101, size=(self.V, self.K)).astype(np.float64)
 
@@ -239,7 +239,7 @@ class ILDA(LDA):
         self.η = np.full(self.I, float(η)) if np.ndim(η) == 0 else np.asarray(η, dtype=np.float64).copy()
         self.D = len(X)
         self._doc_ptr, self._term, self._count = pack_lda(X)
-        self.N = np.array([int(self._count[self._doc_ptr[d]:self._doc_ptr[d + 1]].sum()) for d in range(self.D)], dtype=np.int64)
+        self.N = doc_totals(self._doc_ptr, self._count)
         self._ioff = np.concatenate([[0], np.cumsum([j * self.K for j in self.J])]).astype(np.int64)
         if λ0 is None:
             rng = np.random.default_rng(seed)

@@ -48,8 +48,37 @@ def _as_doc(x):
     return np.asarray(x, dtype=np.int64).reshape(-1, 2)
 
 
+class PackedCorpus:
+    """A corpus that is already in the CSR form the C ABI takes (what pack_lda / pack_mm return), usable wherever a model takes X: the
+    constructors skip the per-document packing, which dominates the host time of corpora of 10^5+ documents (bootstrap.py stacks
+    replicate corpora this way).  M = None: LDA nesting (doc_ptr of D + 1 offsets); M >= 1: MMCTM nesting (pack_mm's layout).
+    Zero counts are allowed and kept."""
+
+    def __init__(self, D, doc_ptr, term, count, M=None):
+        self.D, self.M = int(D), M
+        self.doc_ptr = np.ascontiguousarray(doc_ptr, dtype=np.int64)
+        self.term = np.ascontiguousarray(term, dtype=np.int32)
+        self.count = np.ascontiguousarray(count, dtype=np.int32)
+        if self.doc_ptr.size != (1 if M is None else M) * (self.D + 1) or self.term.size != self.count.size or self.term.size != int(self.doc_ptr[-1]):
+            raise ValueError("PackedCorpus: doc_ptr / term / count do not fit together")
+
+    def __len__(self):
+        return self.D
+
+
+def doc_totals(doc_ptr, count):
+    """N of every [doc_ptr[i], doc_ptr[i + 1]) range of `count` (int64; doc_ptr may hold several modalities' offset blocks back to back:
+    the ranges that straddle two blocks are meaningless and are the caller's to drop)."""
+    csum = np.concatenate([[0], np.cumsum(count, dtype=np.int64)])
+    return csum[doc_ptr[1:]] - csum[doc_ptr[:-1]]
+
+
 def pack_lda(X):
     """X[d] (W_d x 2, 1-based) -> doc_ptr int64[D+1], term int32[nnz] (0-based), count int32[nnz]."""
+    if isinstance(X, PackedCorpus):
+        if X.M is not None:
+            raise ValueError("a PackedCorpus in the MMCTM nesting was given where one LDA corpus is expected")
+        return X.doc_ptr, X.term, X.count
     D = len(X)
     docs = [_as_doc(x) for x in X]
     doc_ptr = np.zeros(D + 1, dtype=np.int64)
@@ -67,6 +96,10 @@ def pack_lda(X):
 
 def pack_mm(X, M):
     """X[d][m] -> modality-major concatenation; doc_ptr is M*(D+1) absolute offsets."""
+    if isinstance(X, PackedCorpus):
+        if X.M != M:
+            raise ValueError("PackedCorpus holds %r modalities, the model %d" % (X.M, M))
+        return X.doc_ptr, X.term, X.count
     D = len(X)
     doc_ptr = np.zeros(M * (D + 1), dtype=np.int64)
     terms, counts = [], []

@@ -438,6 +438,49 @@ int mmm_resample_counts(mmm_ctx* ctx, int D, const int64_t* doc_ptr, const int32
  * in LDS); MMM_ERR_UNSUPPORTED above that; MMM_ERR_ARG for B < 1, a q outside [0, 1], NULL x or q. */
 int mmm_replicate_summary(mmm_ctx* ctx, int B, size_t n, const double* x, int nq, const double* q, double* mean, double* sd, double* quant);
 
+/* ---- matching signatures to a catalogue and across the replicas of a restart batch (no counterpart in the reference, whose README leaves
+ * the step to the user: cosine to the catalogue, then a linear sum assignment) -------------------------------------
+ * Inputs: sig[r][k][v] (R sets of K signatures over V terms, row-major) and cat[c][v] (C catalogue signatures), all finite and >= 0; rows
+ * need NOT be normalised (the cosine is scale-free).
+ * 1. Cosine.  S[r][k][c] = (sum_v sig cat) / (sqrt(sum_v sig^2) sqrt(sum_v cat^2)); a row whose sum of squares is 0 gives S = 0 against
+ *    everything (never NaN).  Each of the three sums is taken in the same order, fixed by V alone: 64 partial sums, partial l over the terms
+ *    l, l + 64, l + 128, ... ascending, combined as a tree -- l with l ^ 1, then with l ^ 2, then the two quads of a group of 8, the two
+ *    halves of a group of 16, and the four groups of 16 as (0 + 2) + (1 + 3); products and sums are separate roundings (no fused
+ *    multiply-add).  Neither R, the chunking of the replicas nor the device enters.
+ * 2. Assignment.  For every r the injective a_r : k -> c that maximises sum_k S[r][k][a_r(k)], by the shortest-augmenting-path algorithm
+ *    of Crouse (IEEE TAES 52(4), 2016, Algorithm 1) on W = -S: rows are inserted in the order k = 0..K-1; the duals u, v start at 0; in a
+ *    search from row i (minval = 0 at first) the reduced cost of an unscanned column c is ((minval + W[i][c]) - u[i]) - v[c] and replaces
+ *    spc[c] (and path[c] = i) only when strictly smaller; the next column is the unscanned c with the smallest spc[c], ties to the lowest
+ *    c; minval = its spc; it is scanned; if it is assigned the search goes on from its row, else it is the sink.  Dual update:
+ *    u[cur] += minval; u[i] += minval - spc[col4row[i]] for the other scanned rows; v[c] -= minval - spc[c] for the scanned columns; then
+ *    the assignment is flipped along `path` from the sink.  Only +, - and compares: given S, the same result on any machine.
+ * 3. Outputs per replica: assign[r][k] (0-based), matched[r][k] = S[r][k][assign[r][k]], optionally S.
+ * 4. Consensus of R replicas against replica `ref`: the catalogue is replica ref's own K signatures (C = K);
+ *    P[r][assign[r][k]][v] = sig[r][k][v] / sum_v sig[r][k][v] (sum in index order; a zero row stays zero) is every replica in the
+ *    labelling of `ref`; mean / sd / quant of P[.][k][v] over the R replicas by the definitions of mmm_replicate_summary ([K][V],
+ *    [K][V], [nq][K][V]); stability[k] = the mean over r != ref, added in replica order, of the matched cosine of the signature of
+ *    replica r that is assigned to k (R = 1: 1.0).
+ * Limits: 1 <= K <= C <= 1024, V >= 1, any R >= 0 (replicas go through the device in chunks, which cannot change a replica's bits; R = 0
+ * writes nothing); the consensus 1 <= R <= 4096.  mmm_signature_cosine alone takes any K, C >= 1.
+ * MMM_ERR_ARG: NULL pointers, K > C, K < 1, a negative or non-finite entry in a caller array, `ref` outside [0, R), q outside [0, 1], a
+ * replica table (handle forms) with a non-finite entry.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 1024, R > 4096 replicas
+ * in a consensus, ILDA / IMMCTM handles (feature-factorised tables). */
+int mmm_signature_cosine(mmm_ctx* ctx, int R, int K, int C, int V, const double* sig, const double* cat, double* S /* [R][K][C] */);
+int mmm_signature_match(mmm_ctx* ctx, int R, int K, int C, int V, const double* sig, const double* cat, int32_t* assign /* [R][K] */,
+                        double* matched /* [R][K] */, double* S /* [R][K][C] or NULL */);
+/* each of assign, matched [R][K], stability [K], mean, sd [K][V], quant [nq][K][V] may be NULL */
+int mmm_signature_consensus(mmm_ctx* ctx, int R, int K, int V, const double* sig, int ref, int nq, const double* q, int32_t* assign,
+                            double* matched, double* stability, double* mean, double* sd, double* quant);
+/* The same on the replicas of a handle (R = mmm_lda_replicas / mmm_ctm_replicas; an ordinary handle is one replica), read where they lie:
+ * LDA: the lambda of every replica (topic k = column k of the V x K table); MMCTM: the gamma of modality `modality`.  cat == NULL: the
+ * catalogue is the selected replica's own topics (C is ignored, C = K).  Only cat goes up and only the outputs come down. */
+int mmm_lda_match_replicas(mmm_lda* m, int C, const double* cat, int32_t* assign, double* matched);
+int mmm_ctm_match_replicas(mmm_ctm* m, int modality, int C, const double* cat, int32_t* assign, double* matched);
+int mmm_lda_replica_consensus(mmm_lda* m, int ref, int nq, const double* q, int32_t* assign, double* matched, double* stability, double* mean,
+                              double* sd, double* quant);
+int mmm_ctm_replica_consensus(mmm_ctm* m, int modality, int ref, int nq, const double* q, int32_t* assign, double* matched, double* stability,
+                              double* mean, double* sd, double* quant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,9 +13,14 @@ from .ctm import (calculate_docmodality_loglikelihood, calculate_modality_loglik
 from .inference import fit_heldout, predict_modality_η, transform
 from .restarts import fit_lda_restarts
 from .bootstrap import BootstrapResult, bootstrap_exposures, replicate_summary, resample_counts
+from .match import (ConsensusResult, SignatureMatch, cosine_similarity, match_restarts, match_signatures, restart_consensus,
+                    signature_consensus)
+from .io import read_signatures_tsv
 from .utils import (PackedCorpus, format_counts_ctm, format_counts_lda, format_counts_mmctm, make_count_matrix, pack_lda,
                     pack_mm, read_counts_tsv, shard_documents)
 
 __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_lda", "format_counts_ctm", "format_counts_mmctm", "Context",
            "MmmError", "build", "fit_restarts", "fit_lda_restarts", "transform", "fit_heldout", "predict_modality_η",
-           "bootstrap_exposures", "resample_counts", "replicate_summary", "BootstrapResult", "PackedCorpus"]
+           "bootstrap_exposures", "resample_counts", "replicate_summary", "BootstrapResult", "PackedCorpus",
+           "cosine_similarity", "match_signatures", "match_restarts", "restart_consensus", "signature_consensus", "SignatureMatch", "ConsensusResult",
+           "read_signatures_tsv"]

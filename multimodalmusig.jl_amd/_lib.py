@@ -133,6 +133,13 @@ _SIGS = {
     "mmm_mixture_loglik_features": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p, i64p, vp, vp, f64p, C.c_int, f64p, C.POINTER(C.c_double)]),
     "mmm_resample_counts": (C.c_int, [vp, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]),
     "mmm_replicate_summary": (C.c_int, [vp, C.c_int, C.c_size_t, vp, C.c_int, vp, vp, vp, vp]),
+    "mmm_signature_cosine": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "mmm_signature_match": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "mmm_signature_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_lda_match_replicas": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    "mmm_ctm_match_replicas": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "mmm_lda_replica_consensus": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_ctm_replica_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

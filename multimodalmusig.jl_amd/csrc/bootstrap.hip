@@ -184,6 +184,20 @@ __global__ __launch_bounds__(kSumThreads) void k_replicate_summary(int B, size_t
 
 } // namespace
 
+static_assert(kSumElems == MMM_SUMMARY_MAX_B, "mmm_internal.h states the limit of the summary");
+
+// the summary on device buffers (mmm_internal.h): the launch of mmm_replicate_summary, also used by the consensus of match.hip
+int mmm_replicate_summary_dev(mmm_ctx* ctx, int B, size_t n, const double* x, int nq, const double* q, double* out)
+{
+    int P = 16;
+    while (P < B) P <<= 1;
+    const size_t C = (size_t)(kSumElems / P), blocks = (n + C - 1) / C;
+    if (blocks > 0x7fffffffull) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_replicate_summary: n = %zu columns need more than 2^31 - 1 blocks", n);
+    hipLaunchKernelGGL(k_replicate_summary, dim3((unsigned)blocks), dim3(kSumThreads), 0, ctx->stream, B, n, P, x, nq, q, out, out + n, out + 2 * n);
+    MMM_LAUNCH_CHECK(ctx);
+    return MMM_OK;
+}
+
 extern "C" {
 
 int mmm_resample_counts(mmm_ctx* ctx, int D, const int64_t* doc_ptr, const int32_t* count, int B, int b0, uint64_t seed, uint32_t stream, int32_t* out)
@@ -249,16 +263,11 @@ int mmm_replicate_summary(mmm_ctx* ctx, int B, size_t n, const double* x, int nq
         return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_replicate_summary: B = %d replicates; a column is sorted in LDS, which holds at most %d", B, kSumElems);
     if (!quant) nq = 0;
     if (n == 0 || (!mean && !sd && nq == 0)) return MMM_OK;
-    int P = 16;
-    while (P < B) P <<= 1;
-    const size_t C = (size_t)(kSumElems / P), blocks = (n + C - 1) / C;
-    if (blocks > 0x7fffffffull) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_replicate_summary: n = %zu columns need more than 2^31 - 1 blocks", n);
     DevBuf<double> xd, qd, od;
     MMM_HIP(ctx, xd.alloc((size_t)B * n)); MMM_HIP(ctx, qd.alloc((size_t)nq)); MMM_HIP(ctx, od.alloc((2 + (size_t)nq) * n));
     MMM_HIP(ctx, hipMemcpyAsync(xd.p, x, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, ctx->stream));
     if (nq) MMM_HIP(ctx, hipMemcpyAsync(qd.p, q, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_replicate_summary, dim3((unsigned)blocks), dim3(kSumThreads), 0, ctx->stream, B, n, P, xd.p, nq, qd.p, od.p, od.p + n, od.p + 2 * n);
-    MMM_LAUNCH_CHECK(ctx);
+    if (int rc = mmm_replicate_summary_dev(ctx, B, n, xd.p, nq, qd.p, od.p)) return rc;
     if (mean) MMM_HIP(ctx, hipMemcpyAsync(mean, od.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (sd) MMM_HIP(ctx, hipMemcpyAsync(sd, od.p + n, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     if (nq) MMM_HIP(ctx, hipMemcpyAsync(quant, od.p + 2 * n, sizeof(double) * (size_t)nq * n, hipMemcpyDeviceToHost, ctx->stream));

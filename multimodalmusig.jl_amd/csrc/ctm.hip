@@ -1736,4 +1736,36 @@ int mmm_ctm_fit_batch(mmm_ctm* m, int maxiter, double tol, int update_sigma, dou
     return MMM_OK;
 }
 
+// ---- signatures of the replicas matched to a catalogue / to one another (match.hip; include/mmmusig.h) --------------------------------------
+// Device pointer of modality `modality`'s gamma of every replica: K_m rows of V_m values, strides (V_m, 1).
+static int ctm_replica_tables(mmm_ctm* m, const char* who, int modality, std::vector<const double*>& tab)
+{
+    int rc = prep(m);
+    if (rc) return rc;
+    if (m->immctm) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "%s: the topics of an IMMCTM handle are factorised over the features; no K x V signatures to match", who);
+    MMM_CHECK(m->ctx, modality >= 0 && modality < m->dm.M, "%s: modality %d of %d", who, modality, m->dm.M);
+    tab.resize((size_t)m->R);
+    for (int r = 0; r < m->R; ++r) tab[(size_t)r] = m->gamma.p + (size_t)r * (size_t)m->GM + (size_t)m->dm.goff[modality];
+    return MMM_OK;
+}
+
+int mmm_ctm_match_replicas(mmm_ctm* m, int modality, int C, const double* cat, int32_t* assign, double* matched)
+{
+    if (!m) return MMM_ERR_ARG;
+    std::vector<const double*> tab;
+    if (int rc = ctm_replica_tables(m, "mmm_ctm_match_replicas", modality, tab)) return rc;
+    return mmm_match_tables(m->ctx, "mmm_ctm_match_replicas", m->R, m->dm.K[modality], C, m->dm.V[modality], tab.data(), (size_t)m->dm.V[modality], 1, cat, m->sel,
+                            assign, matched);
+}
+
+int mmm_ctm_replica_consensus(mmm_ctm* m, int modality, int ref, int nq, const double* q, int32_t* assign, double* matched, double* stability, double* mean,
+                              double* sd, double* quant)
+{
+    if (!m) return MMM_ERR_ARG;
+    std::vector<const double*> tab;
+    if (int rc = ctm_replica_tables(m, "mmm_ctm_replica_consensus", modality, tab)) return rc;
+    return mmm_consensus_tables(m->ctx, "mmm_ctm_replica_consensus", m->R, m->dm.K[modality], m->dm.V[modality], tab.data(), (size_t)m->dm.V[modality], 1, ref, nq,
+                                q, assign, matched, stability, mean, sd, quant);
+}
+
 } // extern "C"

@@ -1665,4 +1665,39 @@ int mmm_lda_fit_batch(mmm_lda* m, int maxiter, double tol, double* ll_hist, int*
     return MMM_OK;
 }
 
+// ---- signatures of the replicas matched to a catalogue / to one another (match.hip; include/mmmusig.h) --------------------------------------
+// Device pointer of every replica's CURRENT lambda: the ring slot mmm_lda_get reads after mmm_lda_select(r) -- the replicas of a batch stop
+// at passes of their own, so the slot differs from replica to replica.  Topic k of a V x K table is the contiguous column k: strides (V, 1).
+static int lda_replica_tables(mmm_lda* m, const char* who, std::vector<const double*>& tab)
+{
+    int rc = prepare_call(m);          // settles the passes in flight, as mmm_lda_get does
+    if (rc) return rc;
+    if (m->ilda) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "%s: the topics of an ILDA handle are factorised over the features; no V x K signatures to match", who);
+    if (m->R > 1) { m->rep_t[(size_t)m->sel] = m->t; m->rep_hist[(size_t)m->sel] = m->n_hist; }
+    tab.resize((size_t)m->R);
+    for (int r = 0; r < m->R; ++r) {
+        const int t = m->R > 1 ? m->rep_t[(size_t)r] : m->t;
+        tab[(size_t)r] = m->lambda[t % 3].p + (size_t)r * m->V * m->K;
+    }
+    return MMM_OK;
+}
+
+int mmm_lda_match_replicas(mmm_lda* m, int C, const double* cat, int32_t* assign, double* matched)
+{
+    if (!m) return MMM_ERR_ARG;
+    std::vector<const double*> tab;
+    if (int rc = lda_replica_tables(m, "mmm_lda_match_replicas", tab)) return rc;
+    return mmm_match_tables(m->ctx, "mmm_lda_match_replicas", m->R, m->K, C, m->V, tab.data(), (size_t)m->V, 1, cat, m->sel, assign, matched);
+}
+
+int mmm_lda_replica_consensus(mmm_lda* m, int ref, int nq, const double* q, int32_t* assign, double* matched, double* stability, double* mean, double* sd,
+                              double* quant)
+{
+    if (!m) return MMM_ERR_ARG;
+    std::vector<const double*> tab;
+    if (int rc = lda_replica_tables(m, "mmm_lda_replica_consensus", tab)) return rc;
+    return mmm_consensus_tables(m->ctx, "mmm_lda_replica_consensus", m->R, m->K, m->V, tab.data(), (size_t)m->V, 1, ref, nq, q, assign, matched, stability, mean,
+                                sd, quant);
+}
+
 } // extern "C"

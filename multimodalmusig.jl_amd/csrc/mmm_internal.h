@@ -211,3 +211,17 @@ int mmm_p2p_check(mmm_ctx* ctx);
 // for kernels that fold the exchange in: the argument block and a fresh sequence number (false: p2p not in use / too large)
 bool mmm_p2p_begin(mmm_ctx* ctx, size_t count, P2PArgs* args, unsigned int* seq);
 void mmm_p2p_release(mmm_ctx* ctx);
+
+// ---- summary over replicates on device buffers (bootstrap.hip): x [B][n], q [nq], out [(2 + nq)][n] = mean, sd, quantiles.  The arguments
+// have been validated by the caller (1 <= B <= MMM_SUMMARY_MAX_B, q in [0, 1]); enqueues on the ctx stream and does not wait.
+constexpr int MMM_SUMMARY_MAX_B = 4096;
+int mmm_replicate_summary_dev(mmm_ctx* ctx, int B, size_t n, const double* x, int nq, const double* q, double* out);
+
+// ---- signature matching (match.hip) for the handle entries of lda.hip / ctm.hip.  h_tab: R device pointers, one per replica; element
+// (k, v) of replica r is h_tab[r][k * sk + v * sv].  cat: host catalogue [C][V], or NULL: replica `self`'s own K signatures (C = K).
+// Host outputs; both wait for the device.
+constexpr int MMM_MATCH_MAX_C = 1024;
+int mmm_match_tables(mmm_ctx* ctx, const char* who, int R, int K, int C, int V, const double* const* h_tab, size_t sk, size_t sv, const double* cat, int self,
+                     int32_t* assign, double* matched);
+int mmm_consensus_tables(mmm_ctx* ctx, const char* who, int R, int K, int V, const double* const* h_tab, size_t sk, size_t sv, int ref, int nq, const double* q,
+                         int32_t* assign, double* matched, double* stability, double* mean, double* sd, double* quant);

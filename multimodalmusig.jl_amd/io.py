@@ -1,6 +1,6 @@
 """Result tables of scripts/run_mmctm.jl:184-245 (`topicdf`/`writesigs`, `propdf`/`writeprops`, `cov2cor`, `writedlm` of μ, Σ)
 without DataFrames: plain TSV written from the model's fields.  The input side (TSV -> count matrices -> CSR) is in utils.py
-(`read_counts_tsv`, `format_counts_*`, `pack_lda`, `pack_mm`)."""
+(`read_counts_tsv`, `format_counts_*`, `pack_lda`, `pack_mm`); `read_signatures_tsv` reads a signature catalogue for match.py."""
 import numpy as np
 
 
@@ -69,3 +69,36 @@ def write_matrix(filename, A):
     with open(filename, "w") as fh:
         for row in A:
             fh.write("\t".join(_fmt(x) for x in row) + "\n")
+
+
+def read_signatures_tsv(path, terms=None):
+    """A signature catalogue in the COSMIC layout -- a header `Type<TAB>SBS1<TAB>SBS2...` (the first column's name is free: `term` in our
+    count tables), then one row per term with one probability per signature -- as (names, terms, S) with S the [C, V] float64 array
+    `match_signatures` takes (one ROW per signature).  Given `terms` (the model's vocabulary, in its order), the columns of S follow that
+    order: catalogue terms that are not asked for are dropped, a term the catalogue lacks raises ValueError."""
+    with open(path) as fh:
+        header = fh.readline().rstrip("\n").split("\t")
+        names = header[1:]
+        file_terms, rows = [], []
+        for n, line in enumerate(fh, start=2):
+            parts = line.rstrip("\n").split("\t")
+            if len(parts) < 2:
+                continue
+            if len(parts) != len(header):
+                raise ValueError("%s line %d: %d fields, the header has %d" % (path, n, len(parts), len(header)))
+            file_terms.append(parts[0]); rows.append([float(x) for x in parts[1:]])
+    if not names:
+        raise ValueError("%s: no signature columns" % path)
+    table = np.asarray(rows, dtype=np.float64).reshape(len(rows), len(names))
+    if terms is None:
+        return names, file_terms, np.ascontiguousarray(table.T)
+    where = {}
+    for i, t in enumerate(file_terms):
+        if t in where:
+            raise ValueError("%s: term %r is listed twice" % (path, t))
+        where[t] = i
+    missing = [t for t in terms if t not in where]
+    if missing:
+        raise ValueError("%s lacks %d of the %d terms asked for (first: %r)" % (path, len(missing), len(terms), missing[0]))
+    idx = np.asarray([where[t] for t in terms], dtype=np.int64)
+    return names, list(terms), np.ascontiguousarray(table[idx].T)

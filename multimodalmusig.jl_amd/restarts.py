@@ -32,14 +32,24 @@ def pick_optimal_model(ll):
     return int(np.argmin(ranks.mean(axis=1)))
 
 
-def fit_seed_models(counts, K, α, V, seeds, batch_size=None, ctx=None, maxiter=1000, tol=1e-4, rank=0, nranks=1, allgather=None, **kw):
+def _one_batch(what, consensus, R, batch_size, nranks):
+    """consensus=True needs every restart in one batch handle on one rank: the restarts are matched to one another where they lie"""
+    if consensus and (nranks > 1 or (batch_size and int(batch_size) < R)):
+        raise ValueError("%s(consensus=True) needs all %d restarts in one batch on one rank (batch_size=None, nranks=1): the consensus is "
+                         "taken over the replicas of one handle" % (what, R))
+
+
+def fit_seed_models(counts, K, α, V, seeds, batch_size=None, ctx=None, maxiter=1000, tol=1e-4, rank=0, nranks=1, allgather=None, consensus=False, **kw):
     """Stage 1 (run_mmctm.jl:97-109): one restart per seed.  Returns (γ of the best restart per modality -- a list over m of
     [K_m, V_m] arrays --, their final log-likelihoods, the [len(seeds), M] matrix of all final log-likelihoods).
+    consensus=True (all restarts in one batch: batch_size None) appends a list over the modalities of the batch's
+    `restart_consensus(model, modality=m)` -- what the sweep says about every topic, against the best restart of that modality.
 
     Several GPUs: restarts are independent, so they are simply dealt out -- rank r of nranks fits seeds[r::nranks] on its own
     context (one WITHOUT a communicator: every rank holds the whole corpus) and the per-modality winners are merged with the
     host's `allgather(obj) -> list of every rank's obj` (torch.distributed.all_gather_object, MPI, ...).  No device collective."""
     seeds = [int(s) for s in seeds]
+    _one_batch("fit_seed_models", consensus, len(seeds), batch_size, nranks)
     if nranks > 1:
         if allgather is None:
             raise ValueError("nranks > 1 needs an allgather callable")
@@ -63,6 +73,7 @@ def fit_seed_models(counts, K, α, V, seeds, batch_size=None, ctx=None, maxiter=
     best_ll = np.full(M, -np.inf)
     best_gamma = [None] * M
     all_ll = np.zeros((R, M))
+    cons = None
     for b0 in range(0, R, bs):
         chunk = seeds[b0:b0 + bs]
         g0 = []
@@ -78,7 +89,12 @@ def fit_seed_models(counts, K, α, V, seeds, batch_size=None, ctx=None, maxiter=
                 best_ll[m] = model.restart_ll[opt[m], m]
                 model.select(opt[m])
                 best_gamma[m] = np.stack([model.γ[m][k] for k in range(K[m])])
+        if consensus:
+            from .match import restart_consensus
+            cons = [restart_consensus(model, modality=m) for m in range(M)]
         model.close()
+    if consensus:
+        return best_gamma, best_ll, all_ll, cons
     return best_gamma, best_ll, all_ll
 
 
@@ -88,15 +104,17 @@ def _best(ll):
     return int(np.argmax(np.where(np.isnan(ll), -np.inf, ll)))
 
 
-def fit_lda_restarts(X, K, α, η, seeds, V=None, batch_size=None, ctx=None, maxiter=1000, tol=1e-4, rank=0, nranks=1, allgather=None):
+def fit_lda_restarts(X, K, α, η, seeds, V=None, batch_size=None, ctx=None, maxiter=1000, tol=1e-4, rank=0, nranks=1, allgather=None, consensus=False):
     """LDA from several random initialisations, keeping the best: restart i is `LDA(K, α, η, [V,] X, seed=seeds[i])`, fitted with
     the others as the replicas of batch handles of at most `batch_size` restarts (all of them by default).  Returns (index of the
     restart with the highest final log-likelihood -- ties to the lowest index --, its λ (V x K), its γ (K x D), the [len(seeds)]
-    final log-likelihoods).
+    final log-likelihoods).  consensus=True (all restarts in one batch: batch_size None) appends the batch's `restart_consensus(model)`:
+    every restart's topics matched to the winner's, their stability and mean / sd / quantiles over the restarts.
 
     Several GPUs: as fit_seed_models -- rank r of nranks fits seeds[r::nranks] on its own context (without a communicator) and
     the results are merged with the host's `allgather(obj) -> list of every rank's obj`; every rank returns the same."""
     seeds = [int(s) for s in seeds]
+    _one_batch("fit_lda_restarts", consensus, len(seeds), batch_size, nranks)
     if nranks > 1:
         if allgather is None:
             raise ValueError("nranks > 1 needs an allgather callable")
@@ -120,6 +138,7 @@ def fit_lda_restarts(X, K, α, η, seeds, V=None, batch_size=None, ctx=None, max
     bs = R if not batch_size else int(batch_size)
     all_ll = np.full(R, np.nan)
     best = None
+    cons = None
     for b0 in range(0, R, bs):
         chunk = seeds[b0:b0 + bs]
         lam0 = [np.random.default_rng(s).integers(1, 101, size=(V, K)).astype(np.float64) for s in chunk]   # LDA(..., seed=s), LDA.jl:36
@@ -130,7 +149,12 @@ def fit_lda_restarts(X, K, α, η, seeds, V=None, batch_size=None, ctx=None, max
         if best is None or _best([all_ll[best[0]], model.restart_ll[i]]) == 1:    # (an equal later batch keeps the earlier index)
             model.select(i)
             best = (b0 + i, model.λ, model.γ)
+        if consensus:
+            from .match import restart_consensus
+            cons = restart_consensus(model)
         model.close()
+    if consensus:
+        return best[0], best[1], best[2], all_ll, cons
     return best[0], best[1], best[2], all_ll
 
 

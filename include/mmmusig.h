@@ -94,7 +94,8 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_LDA_EARLY_PROLOGUE = 1 << 11, /* single-step E-step build: every pass forms its own Elntheta / exp(Elntheta) instead of the previous pass's merged launch */
     MMM_OFF_CTM_PIPE_GAUSS = 1 << 12,    /* Gaussian M-step: the three-barrier-per-column inversion instead of the pipelined one (sum K <= 32); same bits         */
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
-    MMM_OFF_ALL = (1 << 14) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
+    MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
+    MMM_OFF_ALL = (1 << 15) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
 typedef struct {
     int lda_build;        /* MMM_BUILD_*: E-step build of LDA / ILDA handles                                                              */
@@ -221,6 +222,9 @@ int mmm_lda_row_bytes(const mmm_lda* m);
  * E-step kernel of every pass but the first of a call then reads exp(Elntheta) and writes gamma only -- bench.py counts its bytes
  * accordingly), else 0. */
 int mmm_lda_prologue_moved(const mmm_lda* m);
+/* How the single-step E-step build forms a block's lambda statistics: 1 = as a block product B_kv sum_d a_dk r_dv (k_lda_estep_block), 0 = per-wave
+ * LDS slabs (k_lda_estep: MMM_OFF_LDA_BLOCK_STATS, a corpus in which a document lists a term twice, or not the single-step build at all). */
+int mmm_lda_stats_build(const mmm_lda* m);
 /* fit!(model; maxiter, tol) -- LDA.jl:198-224: iterate until |dll|/|ll| < tol after > 10 passes, then ELBO. */
 int mmm_lda_fit(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged,
                 double* elbo);

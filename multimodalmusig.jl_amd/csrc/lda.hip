@@ -261,6 +261,8 @@ struct mmm_lda {
     bool attr_big = false, attr_bigs = false;
     int grid_e = 1, waves_e = 8, grid_s = 1;
     size_t lds_e = 0, lds_tab = 0;
+    bool block_stats = false;   // single-step passes without the E-step ll take k_lda_estep_block (statistics as a block product, no slabs)
+    size_t lds_b = 0; bool attr_b = false;      // its dynamic LDS: table | r | a
     // ILDA (src/ILDA.jl): feature-factorised topics; the V x K rings then hold the effective tables
     bool ilda = false;
     IldaDesc ids{};
@@ -341,9 +343,20 @@ int go_estep3(mmm_lda* m, const EstepArgs& a)
     return MMM_OK;
 }
 
+template <int KPV, int VT, bool RB>
+int go_estep_block(mmm_lda* m, const EstepArgs& a)
+{
+    mmm_ctx* ctx = m->ctx;
+    auto k = k_lda_estep_block<KPV, VT, RB>;
+    if (!m->attr_b) { int rc = set_lds(ctx, k, m->lds_b); if (rc) return rc; m->attr_b = true; }
+    hipLaunchKernelGGL(k, dim3(m->grid_e, RB ? m->R : 1), dim3(m->waves_e * MMM_WAVE), m->lds_b, ctx->stream, a);
+    return MMM_OK;
+}
+
 template <int KPV, int LV, bool LLV, int VT, bool RB>
 int go_estep2(mmm_lda* m, const EstepArgs& a)
 {
+    if constexpr (LV == 16 && KPV <= 12 && !LLV) { if (m->single_step && m->block_stats) return go_estep_block<KPV, VT, RB>(m, a); }
     if constexpr (LV == 16 && KPV <= 12) { if (m->single_step) return go_estep3<KPV, LV, LLV, VT, true, RB>(m, a); }
     return go_estep3<KPV, LV, LLV, VT, false, RB>(m, a);
 }
@@ -944,7 +957,7 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     // Rows of counts (drows): a dense corpus over <= 128 terms is also kept as rows of 16 SL int32 counts -- 4 bytes per term slot against
     // 8 per nonzero -- which the single-step E-step build (96-term vocabularies) and the ll blocks read instead of the padded (term,count)
     // rows: BASELINE config 2 21.2 -> 19.9 us per iteration on the same box.  MMM_LDA_DROWS=0 keeps the (term,count) rows (A/B).
-    bool dense = false, drows = false;
+    bool dense = false, drows = false, dup_terms = false;
     const int SL = dense_slots(V);
     {
         const int build = ctx->tune.lda_build;
@@ -954,7 +967,8 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
         const bool shape = rshape && KP >= 4 && KP * SL <= 64;                               // ... and the dense-row E-step build exists
         const bool dense_enough = 2 * nnz >= (int64_t)D * V;
         bool dup = false;
-        if (rshape && ((shape && dmode != 0) || (drows_env && dense_enough))) {
+        const bool block_shape = L == 16 && KP <= 12 && V <= 96;      // could be single-step: k_lda_estep_block needs every (document, term) listed once
+        if ((rshape && ((shape && dmode != 0) || (drows_env && dense_enough))) || block_shape) {
             std::vector<int> seen((size_t)V, -1);
             for (int d = 0; d < D && !dup; ++d)
                 for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) { if (seen[(size_t)term[e]] == d) { dup = true; break; } seen[(size_t)term[e]] = d; }
@@ -966,6 +980,7 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
         const bool off32 = (int64_t)D * K * 8 < ((int64_t)1 << 32) && (int64_t)D * 16 * (SL + 1) * 4 < ((int64_t)1 << 32);   // the build's 32-bit byte offsets
         dense = shape && !dup && off32 && dmode != 0 && (dmode > 0 || (big && dense_enough));
         drows = drows_env && rshape && !dup && dense_enough;
+        dup_terms = dup;
     }
     const bool small = !dense && (V <= 96) && KP <= 12 && ((D + 12 * G - 1) / (12 * G) <= ncu) && ctx->tune.grid_blocks == 0;
     // single-step build: just enough waves per block to cover the corpus with one block per CU (fewer co-resident waves
@@ -1003,6 +1018,10 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     if (wide) m->grid_e = std::max(1, std::min((D + kWavesPerBlock - 1) / kWavesPerBlock, ncu * blocks_per_cu));     // wave per document
     if (ctx->tune.grid_blocks > 0) m->grid_e = ctx->tune.grid_blocks;
     if ((int64_t)m->grid_e * docs_per_block < D) m->single_step = false;
+    // statistics as a block product (k_lda_estep_block): the single-step geometry above is decided by the slab build's LDS, so that grid,
+    // waves and the association of the cross-block sums are the same whichever build runs; the launch itself asks for what it uses
+    m->block_stats = m->single_step && L == 16 && KP <= 12 && !dup_terms && !mmm_off(ctx->tune, MMM_OFF_LDA_BLOCK_STATS);
+    m->lds_b = sizeof(double) * ((size_t)KP * V + (size_t)m->waves_e * G * (((size_t)V + 15) & ~(size_t)15) + (size_t)m->waves_e * G * KP);
     if (m->dense)      // [16 SL][KP] table | [waves][K][V] slabs | [waves][G][KP] a_k | [waves][64][KP] gamma sums
         m->lds_d = sizeof(double) * ((size_t)16 * SL * KP + (size_t)m->waves_e * 16 * SL * KP + (size_t)m->waves_e * G * KP + (size_t)m->waves_e * MMM_WAVE * KP);
     if (m->dense && m->lds_d > 160 * 1024) { m->dense = false; m->drows = drows && !wide; }      // no dense-row build: rows only if the corpus is dense enough
@@ -1389,6 +1408,8 @@ int mmm_lda_row_bytes(const mmm_lda* m)
 }
 
 int mmm_lda_prologue_moved(const mmm_lda* m) { return (m && m->pro_used) ? 1 : 0; }
+
+int mmm_lda_stats_build(const mmm_lda* m) { return (m && m->block_stats) ? 1 : 0; }
 
 int mmm_lda_ll_history(mmm_lda* m, double* ll, int max_n, int* n)
 {

@@ -211,6 +211,8 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             if (SINGLE) {
 #pragma unroll
                 for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
+                // (waves_per_block pinned below 4: the registers do not cover the table)
+                for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? eB[i] : 0.0;
             }
             __syncthreads();
             first = false;
@@ -345,6 +347,182 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             if constexpr (RB) a.llpart[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
             else a.llpart[blockIdx.x] = s;
         }
+    }
+    MMM_STAMP(7);
+}
+
+
+// ---- single-step E-step, statistics as a block product ------------------------------------------------------------------------------
+// The single-step build of k_lda_estep without its slabs.  phi itself is never needed (k_lda_estep_dense): with s_dv = sum_k a_dk B_kv and
+// r_dv = n_dv / s_dv,   gamma_dk = alpha + a_dk sum_v B_kv r_dv   and the block's statistics are   S_kv = B_kv sum_{d in block} a_dk r_dv,
+// a (K x docs)(docs x V) product over the block's <= 48 documents.  So a term slot costs 2 KP fused multiply-adds and ONE plain 8-byte LDS
+// store of r (no ds_add_f64, no per-wave slab, no slab zeroing, no ten-way slab sum), and after one block barrier thread (v, topic pair)
+// sums a_dk r_dv over the block's documents in increasing d -- an order fixed by (waves per block, V, KP) alone -- and writes B_kv times
+// it where the slab sums went.  The document groups start at chunk 0 (the rotation kept them off each other's slab entries): the four
+// documents of a wave instruction read the same table addresses, which broadcast.
+// A document that lists a term twice would write one sR cell twice: such corpora keep k_lda_estep (mmm_lda::block_stats, set at create).
+// LDS: [KP][V] table | [4 NW][16 ceil(V / 16)] r | [4 NW][KP] a.
+template <int KP>
+__device__ __forceinline__ double lda_chunk_r(const int v, const double n, const bool act, const int V, const double (&av)[KP], double (&acc)[KP],
+                                              const double* __restrict__ sB)
+{
+    const double* bcol = sB + v;
+    double b[KP], s0 = 0.0, s1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) b[k] = bcol[k * V];
+#pragma unroll
+    for (int k = 0; k + 1 < KP; k += 2) { s0 = fma(av[k], b[k], s0); s1 = fma(av[k + 1], b[k + 1], s1); }
+    if (KP & 1) s0 = fma(av[KP - 1], b[KP - 1], s0);
+    const double r = act ? n * dev_rcp(s0 + s1) : 0.0;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[k] = fma(b[k], r, acc[k]);          // padded topics: B = 0
+    return r;
+}
+
+template <int KP, int VT, bool RB = false>
+__global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(EstepArgs a)
+{
+    static_assert(KP <= 12 && KP % 2 == 0, "topic pairs, table of <= 5 registers per thread");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int L = 16, G = MMM_WAVE / L, PRE = 96 / L;
+    MMM_STAMP(0);
+    const int t = a.t;
+    const int stop = rep<RB>(a.ctl, 1)->stop;         // consumed after the prologue (its latency is hidden)
+    const double* __restrict__ gam = a.gamma.s[t % 3];
+    double* __restrict__ gnext = a.gamma.s[(t + 1) % 3];
+    double* __restrict__ Eln = a.Elntheta.s[t % 3];
+    const double* __restrict__ eB = a.expElnbeta.s[(t + 2) % 3];
+    if constexpr (RB) {
+        const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
+        gam = rep<RB>(gam, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD); eB = rep<RB>(eB, VK);
+    }
+    const int K = a.c.K, D = a.c.D;
+    const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
+    const int NCHR = VT ? (VT + L - 1) / L : (V + L - 1) / L;      // chunks of a row (<= PRE: the host takes this build for V <= 96 only)
+    const int Vs = NCHR * L;                          // row stride of sR
+    const int NW = blockDim.x >> 6, ND = NW * G;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int g = lane / L, l = lane % L;
+    double* sB = smem;                                   // [KP][V] exp(Elnbeta_{t-1})
+    double* sR = sB + (size_t)KP * V;                    // [ND][Vs] r_dv = n_dv / sum_k a_dk B_kv (0: term absent, document past D)
+    double* sA = sR + (size_t)ND * Vs;                   // [ND][KP] a_dk
+    double* myR = sR + (size_t)(wid * G + g) * Vs;
+    double* myA = sA + (size_t)(wid * G + g) * KP;
+
+    // ---- document loads are issued before the table is staged (latency overlap), as in k_lda_estep --------------------------------
+    const int d = (blockIdx.x * NW + wid) * G + g;
+    const bool valid = d < D;
+    const bool ext = !RB && a.aexp != nullptr;      // the previous pass's merged launch has formed a = exp(Elntheta) (EstepArgs::aexp)
+    const double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
+    const bool drows = a.c.dense != nullptr || a.c.dense16 != nullptr;      // rows of counts: term = slot
+    const bool rows = drows || a.c.ell != nullptr;
+    const int64_t start = (valid && !rows) ? a.c.doc_ptr[d] : 0;
+    const int W = (valid && !rows) ? (int)(a.c.doc_ptr[d + 1] - start) : 0;
+    constexpr int TB = KP <= 10 ? 4 : 5;            // the table stays in registers until just before the barrier (KP V <= 12 * 96, >= 4 waves; fewer waves: the loop below)
+    double tb[TB];
+#pragma unroll
+    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? eB[i] : 0.0; }
+    // (term,count) rows and CSR visit the listed terms only: every other r is the zero written here, before the barrier the stores come after
+    if (!drows) for (int i = tid; i < ND * Vs; i += blockDim.x) sR[i] = 0.0;
+    MMM_STAMP(1);
+
+    int tv[PRE]; double tn[PRE];      // term slot (-1: none) and count of the lane's chunks
+    const int nch = rows ? NCHR : (W + L - 1) / L;
+    if (drows) {
+        const int* __restrict__ row = a.c.dense + (size_t)(valid ? d : 0) * a.c.Vp;
+        const unsigned short* __restrict__ row16 = a.c.dense16 + (size_t)(valid ? d : 0) * a.c.Vp;
+        const bool h16 = a.c.dense16 != nullptr;
+        const int slp = a.c.Vp >> 4;
+        if (h16) {      // one 16-byte load for the lane's slots
+            const unsigned* __restrict__ r32 = (const unsigned*)(row16 + (size_t)l * slp);
+            const unsigned w0 = r32[0], w1 = r32[1], w2 = r32[2], w3 = r32[3];
+#pragma unroll
+            for (int j = 0; j < PRE; ++j) {
+                const int w = j * L + l;
+                const int n = (valid && j < NCHR && w < V) ? row16_count(w0, w1, w2, w3, j) : 0;
+                tv[j] = n > 0 ? w : -1; tn[j] = (double)n;
+            }
+        } else
+#pragma unroll
+        for (int j = 0; j < PRE; ++j) {
+            const int w = j * L + l;
+            const int n = (valid && j < NCHR && w < V) ? row[row_slot(w, slp)] : 0;
+            tv[j] = n > 0 ? w : -1; tn[j] = (double)n;
+        }
+    } else {
+        const int2* __restrict__ src = rows ? a.c.ell + (size_t)(valid ? d : 0) * V : a.c.tc + start;
+        const int lim = rows ? (valid ? V : 0) : W;
+#pragma unroll
+        for (int j = 0; j < PRE; ++j) {
+            const int w = j * L + l;
+            const int2 p = (j < nch && w < lim) ? src[w] : make_int2(-1, 0);
+            tv[j] = p.x; tn[j] = (double)p.y;
+        }
+    }
+    // ---- Elntheta (LDA.jl:78-80), a_k = exp(Elntheta_k) ------------------------------------------------------------------------------
+    double el = 0.0, al = gk;        // al: the lane's own a_l
+    if (!ext) {
+        const double S = group_sum<L>(gk);
+        const double ps = dev_digamma_pos(l < K ? gk : S);        // lane K of the group holds psi(S)
+        const double psS = __shfl(ps, g * L + K, MMM_WAVE);
+        el = ps - psS;
+        al = (l < K) ? ar_exp(el) : 0.0;
+    }
+    if (l < KP) myA[l] = al;
+    if (stop) return;            // a previous pass met the stopping rule: this launch must not touch the state
+#pragma unroll
+    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
+    for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? eB[i] : 0.0;      // (waves_per_block pinned below 4)
+    __syncthreads();
+    MMM_STAMP(2);
+    if (!ext && valid && l < K) Eln[(size_t)d * K + l] = el;
+    MMM_STAMP(3);
+    // ---- chunk phase: r into sR, the gamma sums without their factor a_k ----------------------------------------------------------------
+    double av[KP], acc[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) { av[k] = myA[k]; acc[k] = 0.0; }
+    int nchmax = nch;
+    if (!rows) {
+        nchmax = max(nchmax, __shfl_xor(nchmax, 32, MMM_WAVE));
+        nchmax = max(nchmax, __shfl_xor(nchmax, 16, MMM_WAVE));
+        nchmax = __builtin_amdgcn_readfirstlane(nchmax);
+    }
+#pragma unroll
+    for (int j = 0; j < PRE; ++j) {
+        if (j < nchmax) {
+            const bool act = tv[j] >= 0;
+            const double r = lda_chunk_r<KP>(act ? tv[j] : 0, tn[j], act, V, av, acc, sB);
+            if (drows) myR[j * L + l] = r;             // every slot of the row, zeros included (slots past V are never read)
+            else if (act) myR[tv[j]] = r;
+        }
+    }
+    MMM_STAMP(4);
+    // ---- gamma_{t+1} = alpha + a_k sum_v B_kv r_v (LDA.jl:83-87 of the next pass) -----------------------------------------------------
+    double mine = 0.0;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) { const double tot = group_sum<L>(acc[k]); if (l == k) mine = tot; }
+    if (valid && l < K) gnext[(size_t)d * K + l] = fma(al, mine, a.c.alpha);
+    MMM_STAMP(5);
+    // ---- block product: T_kv = sum_d a_dk r_dv in increasing d, S_kv = B_kv T_kv -> the block's partial ---------------------------------
+    __syncthreads();
+    MMM_STAMP(6);
+    double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
+    if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
+    for (int i = tid; i < (KP / 2) * V; i += blockDim.x) {
+        const int kp = VT ? i / VT : i / V, v = i - kp * V, k = 2 * kp;
+        const double* rc = sR + v;
+        const double* ac = sA + k;
+        double t0 = 0.0, t1 = 0.0;
+#pragma unroll 2
+        for (int dd = 0; dd < ND; dd += G) {
+            double rr[G], a0[G], a1[G];
+#pragma unroll
+            for (int q = 0; q < G; ++q) { rr[q] = rc[(size_t)(dd + q) * Vs]; a0[q] = ac[(dd + q) * KP]; a1[q] = ac[(dd + q) * KP + 1]; }
+#pragma unroll
+            for (int q = 0; q < G; ++q) { t0 = fma(a0[q], rr[q], t0); t1 = fma(a1[q], rr[q], t1); }
+        }
+        if (k < K) out[k * a.pstride + v] = sB[k * V + v] * t0;
+        if (k + 1 < K) out[(k + 1) * a.pstride + v] = sB[(k + 1) * V + v] * t1;
     }
     MMM_STAMP(7);
 }

@@ -15,7 +15,10 @@ for rep in range(3):
     lib.mmm_diag_lda_stamps.argtypes = [C.c_void_p]
     assert lib.mmm_diag_lda_stamps(st) == 0
     s = np.array(st[:8], dtype=np.int64)
+    # k_lda_estep_block (geometry()["block_stats"] == 1): "step end" is the wait at the block barrier, "epilogue" the block product + partial store
     names = ["loads+tables", "tc prefetch+doc prologue+barrier", "Eln store", "chunks", "gamma reduce", "step end", "epilogue"]
+    if rep == 0:
+        print("   block_stats = %d" % m.geometry()["block_stats"])
     d = np.diff(s)
     rt = np.array(st[8:12], dtype=np.int64)
     print("   block0 real time %.2f us (clock %.2f GHz); last block start +%.2f us, end +%.2f us after block0 start" % (

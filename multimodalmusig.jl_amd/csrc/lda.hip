@@ -53,19 +53,10 @@ struct LdaDev {
     const int2* ell;      // [D][V] rows padded with (-1, 0), or NULL: lets the ll blocks fetch a document's terms without first
                           // waiting for doc_ptr (built when V <= 128 and no document lists a term twice)
     const int* dense;     // [D][16][Vp / 16] rows of counts, LANE-major: the Vp / 16 slots of lane l (terms l, 16 + l, ...) are contiguous, so a lane
-                          // requests its part of a row with one load (row_slot()); or NULL.  The ll blocks read these instead of ell
+                          // requests its part of a row with one load (lda_rows.cuh); or NULL.  The ll blocks read these instead of ell
     int Vp;               // slots per row (16 x slots per lane; 16-bit rows keep an even number of slots per lane)
     const unsigned short* dense16;   // the same rows as 16-bit counts (every count < 65536), or NULL: 2 bytes per term slot
 };
-
-// position of term slot w (lane w % 16, the lane's slot w / 16) in a lane-major row of 16 x slp slots
-__device__ __forceinline__ int row_slot(int w, int slp) { return (w & 15) * slp + (w >> 4); }
-// 16-bit lane-major rows: slot c (0..7) of a lane's part, held as four 32-bit words (ONE 16-byte load; the rows are allocated with 16 bytes to spare)
-__device__ __forceinline__ int row16_count(unsigned w0, unsigned w1, unsigned w2, unsigned w3, int c)
-{
-    const unsigned word = c < 4 ? (c < 2 ? w0 : w1) : (c < 6 ? w2 : w3);
-    return (int)((c & 1) ? word >> 16 : word & 0xffffu);
-}
 
 struct LdaCtl {
     unsigned int ticket;
@@ -199,6 +190,8 @@ __device__ unsigned long long g_ll_times[2][512];
 #define MMM_LLSTAMP(which, lb) do { } while (0)
 #endif
 
+#include "lda_rows.cuh"
+
 #include "lda_estep.cuh"
 
 #include "lda_reduce.cuh"
@@ -282,6 +275,17 @@ struct mmm_lda {
     double* doc(DevBuf<double>* b, int s) const { return b[s].p + (size_t)sel * K * D; }
     LdaCtl* ctlp() const { return ctl.p + sel; }
     double* hist() const { return ll_hist.p + (size_t)sel * cap_hist; }
+    // the ll blocks (lda_ll_block): dynamic LDS -- beta table | theta rows | log table -- and the documents of a block of 16 waves
+    size_t lds_red() const { return sizeof(double) * ((size_t)KP * V + 64 * (size_t)KP + MMM_LOGTAB_N); }
+    int docs_per_ll_block() const { return 16 * (MMM_WAVE / (KP <= 15 ? 16 : (KP <= 31 ? 32 : 64))); }
+    // host mirror once a call's passes are enqueued, assuming no early stop (sync_ctl corrects it).  lag: training passes, whose ll is evaluated
+    // one pass late; frozen-topic passes record the ll of the same pass, and with table_beta their phi is formed from beta (unsmoothed)
+    void passes_enqueued(bool lag, bool table_beta)
+    {
+        inflight = true; lag_ll = lag; phi_table_beta = table_beta;
+        if (!lag) ll_pending = false;
+        phi_valid = false; phi_from_prev = true; gnext_valid = true; theta_valid = false;
+    }
 };
 
 namespace {
@@ -584,18 +588,28 @@ int run_topic_update(mmm_lda* m, bool from_sums)
     return MMM_OK;
 }
 
+// gamma_{t+1} for the first pass of a call: update_γ! (LDA.jl:82-90) from the resident phi, unless an earlier pass has left it.  A batch handle's
+// phi is the constructor's 1/K, the same for every replica (the calls that could change it are refused on batch handles; K <= 32 there)
+int first_gamma(mmm_lda* m)
+{
+    if (m->gnext_valid) return MMM_OK;
+    mmm_ctx* ctx = m->ctx;
+    if (m->R == 1) { int rc = materialise_phi(m); if (rc) return rc; }
+    const size_t KD = (size_t)m->K * m->D;
+    for (int r = 0; r < m->R; ++r)
+        hipLaunchKernelGGL(m->K > 64 ? k_lda_gamma_from_phi_big : k_lda_gamma_from_phi, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p,
+                           m->gamma[(m->t + 1) % 3].p + r * KD, (double*)nullptr);
+    MMM_LAUNCH_CHECK(ctx);
+    m->gnext_valid = true;
+    return MMM_OK;
+}
+
 int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
 {
     mmm_ctx* ctx = m->ctx;
     int rc;
     if ((rc = ensure_hist(m, n_iter))) return rc;
-    if (!m->gnext_valid) {
-        // update_γ! for the first pass (LDA.jl:82-90) from the resident phi
-        if ((rc = materialise_phi(m))) return rc;
-        hipLaunchKernelGGL(m->K > 64 ? k_lda_gamma_from_phi_big : k_lda_gamma_from_phi, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->gamma[(m->t + 1) % 3].p, (double*)nullptr);
-        MMM_LAUNCH_CHECK(ctx);
-        m->gnext_valid = true;
-    }
+    if ((rc = first_gamma(m))) return rc;
     const int VK = m->V * m->K;
     for (int it = 0; it < n_iter; ++it) {
         const int t = m->t + 1;
@@ -614,7 +628,7 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
         // rows padded to a multiple of 16; MMM_OFF_LDA_MERGED keeps the split kernels (A/B, tests)
         bool merged = !mmm_off(m->tune, MMM_OFF_LDA_MERGED) && ll_in_k2 && (r.p2p || !mmm_comm_active(ctx)) && !m->wide && m->V <= 256 &&
                       (!m->ilda || (m->ids.SJ <= 16 && !mmm_comm_active(ctx)));
-        const size_t lds_red = sizeof(double) * ((size_t)m->KP * m->V + 64 * (size_t)m->KP + MMM_LOGTAB_N);      // beta table | theta rows | log table
+        const size_t lds_red = m->lds_red();
         int cap = 0;       // residency of the launch whose blocks wait for each other
         if (merged) {
             const int ai = m->ilda ? 2 : r.p2p;
@@ -636,7 +650,7 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
         if (merged) r.VK = Vp * m->K;
         r.llpart2 = m->llpart2.p; r.ll_in_k2 = ll_in_k2 ? 1 : 0;
         r.ll_cells = via_cells ? m->cells.p + 2 * 512 : nullptr; r.ll_seq = via_cells ? ++m->kseq : 0;
-        const int docs_per_ll_block = 16 * (MMM_WAVE / (m->KP <= 15 ? 16 : (m->KP <= 31 ? 32 : 64)));
+        const int docs_per_ll_block = m->docs_per_ll_block();
         // as many ll blocks as can be resident beside the reduce blocks (cut to the launch's residency below), at least one busy wave each
         const int waves_ll = (m->D + docs_per_ll_block / 16 - 1) / (docs_per_ll_block / 16);
         const int blocks_ll = (m->D + docs_per_ll_block - 1) / docs_per_ll_block;      // split launches (no residency bound): full blocks
@@ -734,10 +748,7 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
         m->t = t;
         m->ll_pending = true;
     }
-    if (n_iter > 0) {
-        m->inflight = true; m->lag_ll = true; m->phi_table_beta = false;
-        m->phi_valid = false; m->phi_from_prev = true; m->gnext_valid = true; m->theta_valid = false;
-    }
+    if (n_iter > 0) m->passes_enqueued(true, false);
     return MMM_OK;
 }
 
@@ -751,18 +762,10 @@ int batch_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
     mmm_ctx* ctx = m->ctx;
     int rc;
     const int R = m->R;
-    if (!m->gnext_valid) {
-        // update_γ! for the first pass from the resident phi (LDA.jl:82-90): the constructor's 1/K, the same for every replica (the calls
-        // that could change it are refused on batch handles)
-        const size_t KD = (size_t)m->K * m->D;
-        for (int r = 0; r < R; ++r)
-            hipLaunchKernelGGL(k_lda_gamma_from_phi, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->gamma[(m->t + 1) % 3].p + r * KD, (double*)nullptr);
-        MMM_LAUNCH_CHECK(ctx);
-        m->gnext_valid = true;
-    }
+    if ((rc = first_gamma(m))) return rc;
     const int VK = m->V * m->K;
-    const size_t lds_red = sizeof(double) * ((size_t)m->KP * m->V + 64 * (size_t)m->KP + MMM_LOGTAB_N);
-    const int docs_per_ll_block = 16 * (MMM_WAVE / (m->KP <= 15 ? 16 : (m->KP <= 31 ? 32 : 64)));
+    const size_t lds_red = m->lds_red();
+    const int docs_per_ll_block = m->docs_per_ll_block();
     const int blocks_ll = (m->D + docs_per_ll_block - 1) / docs_per_ll_block;
     const int nred = (VK + 15) / 16;
     for (int it = 0; it < n_iter; ++it) {
@@ -799,10 +802,7 @@ int batch_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
         m->t = t;
         m->ll_pending = true;
     }
-    if (n_iter > 0) {
-        m->inflight = true; m->lag_ll = true; m->phi_table_beta = false;
-        m->phi_valid = false; m->phi_from_prev = true; m->gnext_valid = true; m->theta_valid = false;
-    }
+    if (n_iter > 0) m->passes_enqueued(true, false);
     return MMM_OK;
 }
 
@@ -813,12 +813,7 @@ int frozen_passes(mmm_lda* m, int n_iter, int unsmoothed, double tol, int conv_b
     mmm_ctx* ctx = m->ctx;
     int rc;
     if ((rc = ensure_hist(m, n_iter))) return rc;
-    if (!m->gnext_valid) {
-        if ((rc = materialise_phi(m))) return rc;
-        hipLaunchKernelGGL(m->K > 64 ? k_lda_gamma_from_phi_big : k_lda_gamma_from_phi, dim3(m->grid_s), dim3(kBlock), 0, ctx->stream, m->dev(), m->phi.p, m->gamma[(m->t + 1) % 3].p, (double*)nullptr);
-        MMM_LAUNCH_CHECK(ctx);
-        m->gnext_valid = true;
-    }
+    if ((rc = first_gamma(m))) return rc;
     const int VK = m->V * m->K;
     const bool comm = mmm_comm_active(ctx);
     for (int it = 0; it < n_iter; ++it) {
@@ -842,10 +837,7 @@ int frozen_passes(mmm_lda* m, int n_iter, int unsmoothed, double tol, int conv_b
         m->n_hist++;
         m->t = t;
     }
-    if (n_iter > 0) {
-        m->inflight = true; m->lag_ll = false; m->ll_pending = false; m->phi_table_beta = unsmoothed != 0;
-        m->phi_valid = false; m->phi_from_prev = true; m->gnext_valid = true; m->theta_valid = false;
-    }
+    if (n_iter > 0) m->passes_enqueued(false, unsmoothed != 0);
     return MMM_OK;
 }
 

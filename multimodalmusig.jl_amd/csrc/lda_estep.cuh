@@ -1,10 +1,37 @@
-// lda_estep.cuh -- the E-step kernels of lda.hip (included there, inside its anonymous namespace): k_lda_estep (CSR / padded rows, LDS slabs)
-// and k_lda_estep_dense (rows of counts, statistics in registers).  LDA.jl:69-108.
+// lda_estep.cuh -- the E-step kernels of lda.hip (included there, inside its anonymous namespace): k_lda_estep (any corpus form, LDS slabs;
+// grid-stride or single-step), k_lda_estep_block (single-step, statistics as a block product, no slabs) and k_lda_estep_dense (rows of
+// counts, statistics in registers).  The first two read documents through lda_row_read (lda_rows.cuh).  LDA.jl:69-108.
 __device__ __forceinline__ void lds_wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+
+// What k_lda_estep and k_lda_estep_block resolve first: the arrays of pass t in their ring slots (replica blockIdx.y's copies in a batch build,
+// rep()) and the block's partial statistics.  (k_lda_estep_dense and the wide kernels of lda_stage.cuh spell their four slots out: through
+// this struct the scalar instructions at their heads come out in another order, and those kernels are kept instruction for instruction.)
+template <bool RB = false>
+struct EstepPass {
+    const double* __restrict__ gam; const double* __restrict__ gprev; double* __restrict__ gnext; double* __restrict__ Eln;
+    const double* __restrict__ eB; const double* __restrict__ bprev;
+    __device__ __forceinline__ explicit EstepPass(const EstepArgs& a)
+        : gam(a.gamma.s[a.t % 3]), gprev(a.gamma.s[(a.t + 2) % 3]), gnext(a.gamma.s[(a.t + 1) % 3]), Eln(a.Elntheta.s[a.t % 3]),
+          eB(a.expElnbeta.s[(a.t + 2) % 3]), bprev(a.beta.s[(a.t + 2) % 3])
+    {
+        if constexpr (RB) {
+            const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
+            gam = rep<RB>(gam, KD); gprev = rep<RB>(gprev, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD);
+            eB = rep<RB>(eB, VK); bprev = rep<RB>(bprev, VK);
+        }
+    }
+    static __device__ __forceinline__ int stop(const EstepArgs& a) { return rep<RB>(a.ctl, 1)->stop; }
+    static __device__ __forceinline__ double* partial(const EstepArgs& a, const int K)
+    {
+        double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
+        if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
+        return out;
+    }
+};
 
 // one chunk of L terms of a document group: phi_kw n_w into the accumulators and the wave's slab, and (LL) the
 // log-likelihood numerator of the previous iteration.  __restrict__ tells the compiler that the slab atomics do not
@@ -67,20 +94,8 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     constexpr int G = MMM_WAVE / L;                   // documents per wave step
     constexpr int PRE = (96 + L - 1) / L;             // chunks prefetched into registers (covers a 96-term document)
     MMM_STAMP(0);
-    const int t = a.t;
-    const int stop = rep<RB>(a.ctl, 1)->stop;         // consumed after the first prologue (its latency is hidden)
-    const double* __restrict__ gam = a.gamma.s[t % 3];
-    const double* __restrict__ gprev = a.gamma.s[(t + 2) % 3];
-    double* __restrict__ gnext = a.gamma.s[(t + 1) % 3];
-    double* __restrict__ Eln = a.Elntheta.s[t % 3];
-    const double* __restrict__ eB = a.expElnbeta.s[(t + 2) % 3];
-    const double* __restrict__ bprev = a.beta.s[(t + 2) % 3];
-    if constexpr (RB) {
-        const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
-        gam = rep<RB>(gam, KD); gprev = rep<RB>(gprev, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD);
-        eB = rep<RB>(eB, VK); bprev = rep<RB>(bprev, VK);
-    }
-
+    const int stop = EstepPass<RB>::stop(a);          // consumed after the first prologue (its latency is hidden)
+    const EstepPass<RB> io(a);
     const int K = a.c.K, D = a.c.D;
     const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
     const int NW = blockDim.x >> 6;
@@ -104,8 +119,8 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     // ext: this pass's prologue (digamma, exp: 2 us of this kernel's 10 at BASELINE config 2, all of it on every wave's dependent chain)
     // has run beside the previous pass's reduction, off the critical path; the same functions on the same lanes, hence the same bits
     const bool ext = SINGLE && !LL && !RB && a.aexp != nullptr;      // (batches have no merged launch, so no prologue formed ahead)
-    double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
-    double gp = (LL && valid && l < K) ? gprev[(size_t)d * K + l] : (l < K ? 1.0 : 0.0);
+    double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? io.gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
+    double gp = (LL && valid && l < K) ? io.gprev[(size_t)d * K + l] : (l < K ? 1.0 : 0.0);
     // Single-step build over padded rows (c.ell: [D][V] (term,count), (-1,0) past the document's end): the document's pairs are
     // addressed by d alone, so their loads leave with the gamma row instead of a memory round trip later (doc_ptr -> tc), every
     // document has the same V / L chunks (static register indices, no per-step shuffles)
@@ -119,12 +134,12 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     double tb[TB];
     if (SINGLE) {
 #pragma unroll
-        for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? eB[i] : 0.0; }
+        for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? io.eB[i] : 0.0; }
     }
     for (int i = tid; i < NW * KP * V; i += blockDim.x) sSlab[i] = 0.0;
     for (int i = tid; i < KP * V; i += blockDim.x) {
-        if (!SINGLE) sB[i] = (i < K * V) ? eB[i] : 0.0;
-        if (LL) sBeta[i] = (i < K * V) ? bprev[i] : 0.0;
+        if (!SINGLE) sB[i] = (i < K * V) ? io.eB[i] : 0.0;
+        if (LL) sBeta[i] = (i < K * V) ? io.bprev[i] : 0.0;
     }
     MMM_STAMP(1);
 
@@ -151,55 +166,13 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             if (G >= 4) nchmax = max(nchmax, __shfl_xor(nchmax, 16, MMM_WAVE));
             nchmax = __builtin_amdgcn_readfirstlane(nchmax);
         }
-        if (drows && (SINGLE || first)) {
-            const int* __restrict__ row = a.c.dense + (size_t)(valid ? d : 0) * a.c.Vp;
-            const unsigned short* __restrict__ row16 = a.c.dense16 + (size_t)(valid ? d : 0) * a.c.Vp;
-            const bool h16 = a.c.dense16 != nullptr;
-            const int slp = a.c.Vp >> 4;
-            if (L == 16 && h16) {      // one 16-byte load instead of one 2-byte load per chunk (six loads whose last waited for the first five)
-                const unsigned* __restrict__ r32 = (const unsigned*)(row16 + (size_t)l * slp);
-                const unsigned w0 = r32[0], w1 = r32[1], w2 = r32[2], w3 = r32[3];
-#pragma unroll
-                for (int j = 0; j < PRE; ++j) {
-                    int c = j + rot; if (c >= NCHR) c -= NCHR;
-                    const int w = c * L + l;
-                    const bool in = valid && j < NCHR && w < V;
-                    const int n = in ? row16_count(w0, w1, w2, w3, c) : 0;
-                    tcp[j] = make_int2(n > 0 ? w : -1, n);
-                }
-            } else
-#pragma unroll
-            for (int j = 0; j < PRE; ++j) {
-                int c = j + rot; if (c >= NCHR) c -= NCHR;
-                const int w = c * L + l;
-                const bool in = valid && j < NCHR && w < V;
-                const int n = in ? (h16 ? (int)row16[row_slot(w, slp)] : row[row_slot(w, slp)]) : 0;
-                tcp[j] = make_int2(n > 0 ? w : -1, n);
-            }
-        } else if (rows && !drows && (SINGLE || first)) {
-            const int2* __restrict__ row = a.c.ell + (size_t)(valid ? d : 0) * V;
-#pragma unroll
-            for (int j = 0; j < PRE; ++j) {
-                int c = j + rot; if (c >= NCHR) c -= NCHR;
-                const int w = c * L + l;
-                tcp[j] = (valid && j < NCHR && w < V) ? row[w] : make_int2(-1, 0);
-            }
-        } else if (!rows && (SINGLE || first)) {               // first step: loads issued before the prologue math (later steps: requested a step ahead)
-#pragma unroll
-            for (int j = 0; j < PRE; ++j) {
-                int c = j + rot; if (c >= nch) c -= nch;
-                const int w = c * L + l;
-                tcp[j] = ((j < nch) && (w < W)) ? tcd[w] : make_int2(-1, 0);
-            }
-        }
+        // first step: loads issued before the prologue math (later steps: requested a step ahead)
+        if (SINGLE || first) lda_row_read<L, PRE, true, true, true>(a.c, drows, rows, d, valid, l, V, nch, rot, start, W, [&](int j, int w, int n) { tcp[j] = make_int2(w, n); });
         // ---- Elntheta (LDA.jl:78-80), a_k = exp(Elntheta_k), theta_{t-1} (LDA.jl:92-94) ------------------------------
         double el = 0.0;
         if (ext) { if (l < KP) myA[l] = gk; }
         else {
-            const double S = group_sum<L>(gk);
-            const double ps = dev_digamma_pos(l < K ? gk : S);        // lane K of the group holds psi(S)
-            const double psS = __shfl(ps, g * L + K, MMM_WAVE);
-            el = ps - psS;
+            el = lda_elntheta<L>(gk, g, l, K);
             if (l < KP) myA[l] = (l < K) ? ar_exp(el) : 0.0;
         }
         if (LL) {
@@ -212,13 +185,13 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
 #pragma unroll
                 for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
                 // (waves_per_block pinned below 4: the registers do not cover the table)
-                for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? eB[i] : 0.0;
+                for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? io.eB[i] : 0.0;
             }
             __syncthreads();
             first = false;
             MMM_STAMP(2);
         } else lds_wave_sync();
-        if (!ext && valid && l < K) Eln[(size_t)d * K + l] = el;
+        if (!ext && valid && l < K) io.Eln[(size_t)d * K + l] = el;
         MMM_STAMP(3);
         // ---- requests of the next two steps (grid-stride build) ---------------------------------------------------------
         int2 tcn[PRE];
@@ -228,50 +201,9 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
         if (more) {
             const int nch1 = rows ? NCHR : (W1 + L - 1) / L;
             const int rot1 = nch1 > 0 ? g % nch1 : 0;
-            const int2* __restrict__ tcd1 = a.c.tc + start1;
-            if (drows) {
-                const int* __restrict__ row = a.c.dense + (size_t)(valid1 ? d1 : 0) * a.c.Vp;
-                const unsigned short* __restrict__ row16 = a.c.dense16 + (size_t)(valid1 ? d1 : 0) * a.c.Vp;
-                const bool h16 = a.c.dense16 != nullptr;
-                const int slp = a.c.Vp >> 4;
-                if (L == 16 && h16) {
-                    const unsigned* __restrict__ r32 = (const unsigned*)(row16 + (size_t)l * slp);
-                    const unsigned w0 = r32[0], w1 = r32[1], w2 = r32[2], w3 = r32[3];
-#pragma unroll
-                    for (int j = 0; j < PRE; ++j) {
-                        int c = j + rot1; if (c >= NCHR) c -= NCHR;
-                        const int w = c * L + l;
-                        const bool in = valid1 && j < NCHR && w < V;
-                        const int n = in ? row16_count(w0, w1, w2, w3, c) : 0;
-                        tcn[j] = make_int2(n > 0 ? w : -1, n);
-                    }
-                } else
-#pragma unroll
-                for (int j = 0; j < PRE; ++j) {
-                    int c = j + rot1; if (c >= NCHR) c -= NCHR;
-                    const int w = c * L + l;
-                    const bool in = valid1 && j < NCHR && w < V;
-                    const int n = in ? (h16 ? (int)row16[row_slot(w, slp)] : row[row_slot(w, slp)]) : 0;
-                    tcn[j] = make_int2(n > 0 ? w : -1, n);
-                }
-            } else if (rows) {
-                const int2* __restrict__ row = a.c.ell + (size_t)(valid1 ? d1 : 0) * V;
-#pragma unroll
-                for (int j = 0; j < PRE; ++j) {
-                    int c = j + rot1; if (c >= NCHR) c -= NCHR;
-                    const int w = c * L + l;
-                    tcn[j] = (valid1 && j < NCHR && w < V) ? row[w] : make_int2(-1, 0);
-                }
-            } else {
-#pragma unroll
-            for (int j = 0; j < PRE; ++j) {
-                int c = j + rot1; if (c >= nch1) c -= nch1;
-                const int w = c * L + l;
-                tcn[j] = ((j < nch1) && (w < W1)) ? tcd1[w] : make_int2(-1, 0);
-            }
-            }
-            gkn = (valid1 && l < K) ? gam[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
-            gpn = (LL && valid1 && l < K) ? gprev[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
+            lda_row_read<L, PRE, true, true, true>(a.c, drows, rows, d1, valid1, l, V, nch1, rot1, start1, W1, [&](int j, int w, int n) { tcn[j] = make_int2(w, n); });
+            gkn = (valid1 && l < K) ? io.gam[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
+            gpn = (LL && valid1 && l < K) ? io.gprev[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
             d2 = base + 2 * stride + g; valid2 = (base + 2 * stride < D) && d2 < D;
             start2 = (valid2 && !rows) ? a.c.doc_ptr[d2] : 0;
             W2 = (valid2 && !rows) ? (int)(a.c.doc_ptr[d2 + 1] - start2) : 0;
@@ -310,7 +242,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             double mine = 0.0;
 #pragma unroll
             for (int k = 0; k < KP; ++k) { const double tot = group_sum<L>(acc[k]); if (l == k) mine = tot; }
-            if (valid && l < K) gnext[(size_t)d * K + l] = a.c.alpha + mine;
+            if (valid && l < K) io.gnext[(size_t)d * K + l] = a.c.alpha + mine;
         }
         MMM_STAMP(5);
         if (SINGLE) break;
@@ -328,8 +260,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     if (LL) ll_acc = wave_sum(ll_acc);
     __syncthreads();
     if (LL && lane == 0) sA[wid] = ll_acc;      // sA is free now
-    double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
-    if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
+    double* out = EstepPass<RB>::partial(a, K);
     for (int i = tid; i < K * V; i += blockDim.x) {
         double v8[kMaxWavesE];
 #pragma unroll
@@ -386,16 +317,8 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int L = 16, G = MMM_WAVE / L, PRE = 96 / L;
     MMM_STAMP(0);
-    const int t = a.t;
-    const int stop = rep<RB>(a.ctl, 1)->stop;         // consumed after the prologue (its latency is hidden)
-    const double* __restrict__ gam = a.gamma.s[t % 3];
-    double* __restrict__ gnext = a.gamma.s[(t + 1) % 3];
-    double* __restrict__ Eln = a.Elntheta.s[t % 3];
-    const double* __restrict__ eB = a.expElnbeta.s[(t + 2) % 3];
-    if constexpr (RB) {
-        const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
-        gam = rep<RB>(gam, KD); gnext = rep<RB>(gnext, KD); Eln = rep<RB>(Eln, KD); eB = rep<RB>(eB, VK);
-    }
+    const int stop = EstepPass<RB>::stop(a);          // consumed after the prologue (its latency is hidden)
+    const EstepPass<RB> io(a);
     const int K = a.c.K, D = a.c.D;
     const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
     const int NCHR = VT ? (VT + L - 1) / L : (V + L - 1) / L;      // chunks of a row (<= PRE: the host takes this build for V <= 96 only)
@@ -413,7 +336,7 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     const int d = (blockIdx.x * NW + wid) * G + g;
     const bool valid = d < D;
     const bool ext = !RB && a.aexp != nullptr;      // the previous pass's merged launch has formed a = exp(Elntheta) (EstepArgs::aexp)
-    const double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
+    const double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? io.gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
     const bool drows = a.c.dense != nullptr || a.c.dense16 != nullptr;      // rows of counts: term = slot
     const bool rows = drows || a.c.ell != nullptr;
     const int64_t start = (valid && !rows) ? a.c.doc_ptr[d] : 0;
@@ -421,61 +344,28 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     constexpr int TB = KP <= 10 ? 4 : 5;            // the table stays in registers until just before the barrier (KP V <= 12 * 96, >= 4 waves; fewer waves: the loop below)
     double tb[TB];
 #pragma unroll
-    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? eB[i] : 0.0; }
+    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? io.eB[i] : 0.0; }
     // (term,count) rows and CSR visit the listed terms only: every other r is the zero written here, before the barrier the stores come after
     if (!drows) for (int i = tid; i < ND * Vs; i += blockDim.x) sR[i] = 0.0;
     MMM_STAMP(1);
 
     int tv[PRE]; double tn[PRE];      // term slot (-1: none) and count of the lane's chunks
     const int nch = rows ? NCHR : (W + L - 1) / L;
-    if (drows) {
-        const int* __restrict__ row = a.c.dense + (size_t)(valid ? d : 0) * a.c.Vp;
-        const unsigned short* __restrict__ row16 = a.c.dense16 + (size_t)(valid ? d : 0) * a.c.Vp;
-        const bool h16 = a.c.dense16 != nullptr;
-        const int slp = a.c.Vp >> 4;
-        if (h16) {      // one 16-byte load for the lane's slots
-            const unsigned* __restrict__ r32 = (const unsigned*)(row16 + (size_t)l * slp);
-            const unsigned w0 = r32[0], w1 = r32[1], w2 = r32[2], w3 = r32[3];
-#pragma unroll
-            for (int j = 0; j < PRE; ++j) {
-                const int w = j * L + l;
-                const int n = (valid && j < NCHR && w < V) ? row16_count(w0, w1, w2, w3, j) : 0;
-                tv[j] = n > 0 ? w : -1; tn[j] = (double)n;
-            }
-        } else
-#pragma unroll
-        for (int j = 0; j < PRE; ++j) {
-            const int w = j * L + l;
-            const int n = (valid && j < NCHR && w < V) ? row[row_slot(w, slp)] : 0;
-            tv[j] = n > 0 ? w : -1; tn[j] = (double)n;
-        }
-    } else {
-        const int2* __restrict__ src = rows ? a.c.ell + (size_t)(valid ? d : 0) * V : a.c.tc + start;
-        const int lim = rows ? (valid ? V : 0) : W;
-#pragma unroll
-        for (int j = 0; j < PRE; ++j) {
-            const int w = j * L + l;
-            const int2 p = (j < nch && w < lim) ? src[w] : make_int2(-1, 0);
-            tv[j] = p.x; tn[j] = (double)p.y;
-        }
-    }
+    lda_row_read<L, PRE, false, true, true>(a.c, drows, rows, d, valid, l, V, nch, 0, start, W, [&](int j, int w, int n) { tv[j] = w; tn[j] = (double)n; });
     // ---- Elntheta (LDA.jl:78-80), a_k = exp(Elntheta_k) ------------------------------------------------------------------------------
     double el = 0.0, al = gk;        // al: the lane's own a_l
     if (!ext) {
-        const double S = group_sum<L>(gk);
-        const double ps = dev_digamma_pos(l < K ? gk : S);        // lane K of the group holds psi(S)
-        const double psS = __shfl(ps, g * L + K, MMM_WAVE);
-        el = ps - psS;
+        el = lda_elntheta<L>(gk, g, l, K);
         al = (l < K) ? ar_exp(el) : 0.0;
     }
     if (l < KP) myA[l] = al;
     if (stop) return;            // a previous pass met the stopping rule: this launch must not touch the state
 #pragma unroll
     for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
-    for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? eB[i] : 0.0;      // (waves_per_block pinned below 4)
+    for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? io.eB[i] : 0.0;      // (waves_per_block pinned below 4)
     __syncthreads();
     MMM_STAMP(2);
-    if (!ext && valid && l < K) Eln[(size_t)d * K + l] = el;
+    if (!ext && valid && l < K) io.Eln[(size_t)d * K + l] = el;
     MMM_STAMP(3);
     // ---- chunk phase: r into sR, the gamma sums without their factor a_k ----------------------------------------------------------------
     double av[KP], acc[KP];
@@ -501,13 +391,12 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     double mine = 0.0;
 #pragma unroll
     for (int k = 0; k < KP; ++k) { const double tot = group_sum<L>(acc[k]); if (l == k) mine = tot; }
-    if (valid && l < K) gnext[(size_t)d * K + l] = fma(al, mine, a.c.alpha);
+    if (valid && l < K) io.gnext[(size_t)d * K + l] = fma(al, mine, a.c.alpha);
     MMM_STAMP(5);
     // ---- block product: T_kv = sum_d a_dk r_dv in increasing d, S_kv = B_kv T_kv -> the block's partial ---------------------------------
     __syncthreads();
     MMM_STAMP(6);
-    double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
-    if constexpr (RB) out += (size_t)blockIdx.y * gridDim.x * K * a.pstride;
+    double* out = EstepPass<RB>::partial(a, K);
     for (int i = tid; i < (KP / 2) * V; i += blockDim.x) {
         const int kp = VT ? i / VT : i / V, v = i - kp * V, k = 2 * kp;
         const double* rc = sR + v;

@@ -114,16 +114,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
         const unsigned* row = at_byte((const unsigned*)c.dense16, (dl * 16u + (unsigned)l) * (unsigned)(c.Vp >> 4) * 2u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) wq[j] = row[j];
-    } else if (dense) {
-        const int* __restrict__ row = c.dense + (size_t)(valid ? d : 0) * c.Vp;
-        const unsigned short* __restrict__ row16 = c.dense16 + (size_t)(valid ? d : 0) * c.Vp;
-#pragma unroll
-        for (int j = 0; j < PRE; ++j) pre[j] = (valid && j * L + l < V) ? make_int2(j * L + l, h16 ? (int)row16[row_slot(j * L + l, c.Vp >> 4)] : row[row_slot(j * L + l, c.Vp >> 4)]) : make_int2(-1, 0);
-    } else if (ell) {
-        const int2* __restrict__ row = c.ell + (size_t)(valid ? d : 0) * V;
-#pragma unroll
-        for (int j = 0; j < PRE; ++j) pre[j] = (valid && j * L + l < V) ? row[j * L + l] : make_int2(-1, 0);
-    }
+    } else if (ell) lda_row_read<L, PRE, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
     int64_t start = (!ell && valid) ? c.doc_ptr[d] : 0;
     int W = (!ell && valid) ? (int)(c.doc_ptr[d + 1] - start) : 0;
     // term-major copy [v][KP] of beta_{t-1}: a lane reads the KP entries of its term as 16-byte pairs at immediate offsets (lane stride
@@ -164,13 +155,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
                 if (j < nch) {
                     const unsigned cq = (j & 1) ? w[j / 2] >> 16 : w[j / 2] & 0xffffu;
                     const bool act = valid && j * L + l < V;
-                    const double* bc = sBeta + (size_t)(act ? j * L + l : 0) * KP;
-                    double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-                    for (int k = 0; k + 1 < KP; k += 2) { p0 = fma(tv[k], bc[k], p0); p1 = fma(tv[k + 1], bc[k + 1], p1); }
-                    if (KP & 1) p0 = fma(tv[KP - 1], bc[KP - 1], p0);
-                    const double p = act ? p0 + p1 : 1.0;
-                    acc = fma((double)cq, dev_log_tab(p, sLog), acc);
+                    acc = lda_ll_term<KP>(tv, sBeta + (size_t)(act ? j * L + l : 0) * KP, act, (double)cq, sLog, acc);
                 }
             }
             asm volatile("" : "+v"(acc) :: "memory");
@@ -188,16 +173,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
             if (base != wslot * G) {
                 d = base + g; valid = d < D;
                 gp = (valid && l < K) ? gprev[(size_t)d * K + l] : (l < K ? 1.0 : 0.0);
-                if (dense) {
-                    const int* __restrict__ row = c.dense + (size_t)(valid ? d : 0) * c.Vp;
-                    const unsigned short* __restrict__ row16 = c.dense16 + (size_t)(valid ? d : 0) * c.Vp;
-#pragma unroll
-                    for (int j = 0; j < PRE; ++j) pre[j] = (valid && j * L + l < V) ? make_int2(j * L + l, h16 ? (int)row16[row_slot(j * L + l, c.Vp >> 4)] : row[row_slot(j * L + l, c.Vp >> 4)]) : make_int2(-1, 0);
-                } else {
-                    const int2* __restrict__ row = c.ell + (size_t)(valid ? d : 0) * V;
-#pragma unroll
-                    for (int j = 0; j < PRE; ++j) pre[j] = (valid && j * L + l < V) ? row[j * L + l] : make_int2(-1, 0);
-                }
+                lda_row_read<L, PRE, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
             }
             const double Sp = group_sum<L>(gp);
             lds_wave_sync();
@@ -211,13 +187,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
                 if (j >= nch) break;
                 const int2 t = pre[j];
                 const bool act = t.x >= 0;
-                const double* bc = sBeta + (size_t)(act ? t.x : 0) * KP;
-                double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-                for (int k = 0; k + 1 < KP; k += 2) { p0 = fma(tv[k], bc[k], p0); p1 = fma(tv[k + 1], bc[k + 1], p1); }
-                if (KP & 1) p0 = fma(tv[KP - 1], bc[KP - 1], p0);
-                const double p = act ? p0 + p1 : 1.0;
-                acc = fma((double)t.y, dev_log_tab(p, sLog), acc);
+                acc = lda_ll_term<KP>(tv, sBeta + (size_t)(act ? t.x : 0) * KP, act, (double)t.y, sLog, acc);
             }
         }
     } else
@@ -244,13 +214,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
             const int w = j * L + l;
             const bool act = w < W;
             const int2 t = act ? tcd[w] : make_int2(0, 0);
-            const double* bc = sBeta + (size_t)t.x * KP;
-            double p0 = 0.0, p1 = 0.0;
-#pragma unroll
-            for (int k = 0; k + 1 < KP; k += 2) { p0 = fma(tv[k], bc[k], p0); p1 = fma(tv[k + 1], bc[k + 1], p1); }
-            if (KP & 1) p0 = fma(tv[KP - 1], bc[KP - 1], p0);
-            const double p = act ? p0 + p1 : 1.0;
-            acc = fma((double)t.y, dev_log_tab(p, sLog), acc);
+            acc = lda_ll_term<KP>(tv, sBeta + (size_t)t.x * KP, act, (double)t.y, sLog, acc);
         }
     }
     MMM_RSTAMP(lb == 0 && tid == 0, 22);       // sweep done
@@ -412,10 +376,7 @@ __global__ __launch_bounds__(1024) void k_lda_reduce_ll_mstep(ReduceArgs r, LdaD
         if constexpr (KP <= 12) {
             if (ms.pro) {          // Elntheta_{t+1}, exp(Elntheta_{t+1}) (LDA.jl:78-80): the operations of the E-step kernel's prologue
                 const int lane = tid & 63, g = lane >> 4, l = lane & 15, K = c.K;
-                const double S = group_sum<16>(gnx);
-                const double ps = dev_digamma_pos(l < K ? gnx : S);        // lane K of the group holds psi(S)
-                const double psS = __shfl(ps, g * 16 + K, MMM_WAVE);
-                const double el = ps - psS;
+                const double el = lda_elntheta<16>(gnx, g, l, K);
                 if (pd < c.D && l < K) { ms.pro_Eln[(size_t)pd * K + l] = el; ms.pro_a[(size_t)pd * K + l] = ar_exp(el); }
             }
         }

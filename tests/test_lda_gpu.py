@@ -317,11 +317,15 @@ def test_random_shapes_every_estep_build_against_oracle(mmm, oracle, tuning, idx
         g.close()
 
 
-@pytest.mark.parametrize("env", [{}, {"lda_build": "dense"}, {"disable": ("lda_count_rows",)}, {"disable": ("lda_rows16",)}, {"disable": ("lda_padded_rows",)}])
+_ROW_ENVS = [{}, {"lda_build": "dense"}, {"disable": ("lda_count_rows",)}, {"disable": ("lda_rows16",)}, {"disable": ("lda_padded_rows",)}]
+
+
+@pytest.mark.parametrize("env", _ROW_ENVS + [dict(e, grid_blocks=3) for e in _ROW_ENVS])
 def test_rows_of_counts_with_a_count_beyond_16_bits(mmm, oracle, tuning, env):
     """Dense corpora are also kept as rows of counts (16-bit where every count fits, else 32-bit) for the single-step E-step build, the ll
     blocks and the dense-row build; one count of 70,000 forces the 32-bit rows; every switch that selects another data path gives the
-    oracle's fit."""
+    oracle's fit.  With three blocks the grid-stride build walks the same corpus forms: its loader of the step requested ahead sees 16-bit
+    rows, 32-bit rows, (term,count) rows and CSR."""
     tuning(**env)
     for big in (False, True):
         X, lam0 = np_ref.synth_lda(300, 96, 10, seed=21, mean_n=900)

@@ -180,8 +180,8 @@ size_t estep_lds(const mmm_ctm* m, int flags)     // theta phase
 
 // shard sizes (documents, on a 256-CU device) below which the solve phase takes more lanes per document (create_impl; measured: profiles/r05_solve_layouts.jsonl)
 constexpr int kSolve10Lanes8Below = 75000;      // sum K = 10: 2 lanes x 5 coordinates -> 8 lanes x 2
-constexpr int kSolve28Lanes32Below = 9000;
-constexpr int kSolve28Waves4From = 40000;         // sum K = 28 as 16 x 2: three -> four persistent waves per SIMD        // sum K = 28: 16 lanes x 2 coordinates -> 32 lanes x 1
+constexpr int kSolve28Lanes32Below = 9000;        // sum K = 28: 16 lanes x 2 coordinates -> 32 lanes x 1
+constexpr int kSolve28Waves4From = 40000;         // sum K = 28 as 16 x 2: three -> four persistent waves per SIMD
 
 // LDS of the Gaussian M-step block: the augmented matrix twice (block_inverse_pipelined, sum K <= 32) or A and its inverse (block_inverse_wide)
 inline size_t gauss_lds_doubles(int MK) { return (size_t)(MK <= 32 ? 4 : 2) * MK * MK; }
@@ -886,7 +886,11 @@ int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, c
             // enough that those layouts leave SIMDs without a wave or slots without a document -- takes more lanes per document
             // (profiles/r05_shard_sizes.jsonl: sum K = 10 at 12,505 documents 2 x 5 -> 8 x 2; sum K = 28 at 6,249 documents 16 x 2 -> 32 x 1).
             if (dm.MK == 10) {
-                const bool wide8 = want == 8 || (want == 0 && (int64_t)D * R < kSolve10Lanes8Below * (ncu / 256.0));      // (a restart batch fills the chip with its replicas)
+                // The two sum K = 10 layouts associate a document's sums differently, so this choice decides bits: it is made from D alone, and
+                // a restart batch takes what a single handle on the same corpus takes (replica r is bitwise the single fit of its gamma0).  The
+                // sum K = 28 choices below change no bit (both layouts associate as the 32-lane butterfly does; the wave count only deals the
+                // documents out) and count the replicas that fill the chip, D * R.
+                const bool wide8 = want == 8 || (want == 0 && D < kSolve10Lanes8Below * (ncu / 256.0));
                 if (wide8) { m->Ls = 8; m->cpl = 2; m->lam_occ = 3; } else { m->Ls = 2; m->cpl = 5; m->lam_occ = 2; }
                 m->persist = true;
             } else if (dm.MK == 28) {

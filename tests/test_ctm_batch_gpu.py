@@ -37,7 +37,8 @@ def test_batched_fit_is_bitwise_the_single_model_fit(mmm, case):
         D, K, V, means, feats = 40, [40, 40], [60, 40], [900, 300], None
     elif case == "mm":
         D, K, V, means, feats = 70, [5, 4], [40, 24], [600, 80], None
-    elif case == "imm10":       # sum K = 10: the several-coordinates-per-lane solve kernel (persistent waves, slot refill) with replicas on grid.y
+    elif case == "imm10":       # sum K = 10: the several-coordinates-per-lane solve kernel (persistent waves, slot refill) with replicas on grid.y,
+                                # in its 8 lanes x 2 coordinates layout (150 documents); 2 x 5 and both sides of the switch: test_ctm_dispatch_gpu.py
         D, K, V, means, feats = 150, [10], [96], [1500], SNV3
     elif case == "mm66":        # sum K = 12: the packed solve groups
         D, K, V, means, feats = 70, [6, 6], [40, 24], [600, 80], None

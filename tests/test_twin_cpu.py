@@ -205,6 +205,34 @@ def test_rows_of_counts_theta_phase_changes_only_rounding(oracle):
     assert not np.array_equal(res[1][0], res[0][0])          # ... and it IS another association
 
 
+@pytest.mark.parametrize("case,layouts,differ", [("imm10", ((8, 2), (2, 5)), True), ("mm55", ((8, 2), (2, 5)), True),
+                                                 ("cfg4_lanes", ((32, 1), (16, 2)), False)])
+def test_solve_layouts_sum_k_10_differ_sum_k_28_do_not(oracle, case, layouts, differ):
+    """What tests/test_ctm_dispatch_gpu.py rests on, shown on the order-matched oracle alone at that file's shapes, gamma0 and stopping rule
+    (the device equals this oracle bit for bit per layout).  Sum K = 10: the fits under 8 lanes x 2 coordinates and under 2 x 5 differ in
+    lambda's bits for every restart, so a batch that took the other layout than its single fits cannot pass the device comparison
+    vacuously.  Sum K = 28: 32 x 1 and 16 x 2 associate a document's sums alike -- history, pass count, lambda, nu and the globals equal
+    in every bit -- which is why that choice may count the restarts."""
+    from test_ctm_dispatch_gpu import GEO4, R, _flat, walk_case
+    c = walk_case(case)
+    kw = dict(features=c["feats"]) if c["feats"] is not None else dict(V=c["V"])
+    for r in range(R):
+        fits = []
+        for Ls, cpl in layouts:
+            o = oracle.CtmOracle(c["K"], [0.1] * len(c["K"]), c["X"], gamma0=_flat(c["g0"][r]), geometry=dict(GEO4[case], Ls=Ls, cpl=cpl), **kw)
+            fits.append((o, o.fit(maxiter=30, tol=2e-3)))
+        (a, ha), (b, hb) = fits
+        n = int((a.lam.view(np.int64) != b.lam.view(np.int64)).sum())
+        print("%s restart %d: %d / %d passes, %d of %d lambda values differ in their bits" % (case, r, len(ha), len(hb), n, a.lam.size))
+        if differ:
+            assert n > 0
+        else:
+            assert n == 0 and np.array_equal(ha, hb) and a.elbo_value == b.elbo_value
+            for f in ("nu", "zeta", "mu", "Sigma", "invSigma", "gamma"):
+                assert np.array_equal(getattr(a, f), getattr(b, f)), f
+            assert np.array_equal(a.nev_nu, b.nev_nu) and np.array_equal(a.nev_lambda, b.nev_lambda)
+
+
 def test_table_functions_at_every_table_boundary_and_over_the_range_the_solves_reach(oracle):
     """The order-matched oracle shares `ar_exp_tab` / `ar_log_tab` / `ar_digamma_pos_tab` (csrc/mmm_arith.h + the generated tables) with the
     kernels, so a wrong table entry or a reduction that breaks at an interval boundary would be common to both sides and invisible to the

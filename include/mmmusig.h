@@ -485,6 +485,46 @@ int mmm_lda_replica_consensus(mmm_lda* m, int ref, int nq, const double* q, int3
 int mmm_ctm_replica_consensus(mmm_ctm* m, int modality, int ref, int nq, const double* q, int32_t* assign, double* matched, double* stability,
                               double* mean, double* sd, double* quant);
 
+/* ---- choosing the number of signatures by held-out mutations (no counterpart in the reference, which takes K as given; DESIGN.md section
+ * 4.12).  A document's mutations are dealt into F folds, models are fitted on F - 1 of them (the existing restart batches) and scored on
+ * the fold they did not see.  The two array entries need no model and no communicator; the handle entry scores every restart of a batch
+ * where its tables lie. */
+/* Partition every document's mutations into F folds.  out[f * nnz + e], f < F: the number of mutations of entry e that fall in fold f.
+ * The N_d mutations of document d are numbered i = 0 .. N_d - 1 in CSR order: with cum the inclusive prefix sums of the document's counts,
+ * mutation i lies in the entry e with cum[e-1] <= i < cum[e].  Its fold is (uint64(u_i) * F) >> 32, where u_i is output word i % 4 of the
+ * Philox4x32-10 block (constants as for mmm_resample_counts) with key = (seed low 32 bits, seed high 32 bits) and counter =
+ * (i / 4, d, rep, 0x80000000 | stream): the high bit of the fourth counter word keeps a split from sharing its random words with a
+ * resample of the same seed, hence stream < 2^31.  `rep` numbers repeated splits of one seed.
+ * It follows that sum_f out[f][e] = count[e] exactly; the sparsity pattern is kept (an entry may come out 0 in a fold, as with the
+ * resampler); the same arguments give the same bits on every run and under every launch geometry (integer arithmetic only).
+ * MMM_ERR_ARG: NULL pointer, negative count, doc_ptr[0] != 0 or decreasing doc_ptr, F outside 1..64, rep < 0, stream >= 2^31;
+ * MMM_ERR_UNSUPPORTED: some N_d >= 2^31.  nnz = 0: MMM_OK, nothing written. */
+int mmm_split_counts(mmm_ctx* ctx, int D, const int64_t* doc_ptr, const int32_t* count, int F, int rep, uint64_t seed, uint32_t stream,
+                     int32_t* out);
+/* Per-document log-likelihood and reconstruction cosine of a CSR corpus under proportions props [k + K d] and a table phi [k V + v], as
+ * mmm_mixture_loglik takes them.  With p_v = sum_k props[k + K d] * phi[k V + v], k ascending, product and sum rounded separately:
+ *   ll_doc[d] = sum_e n_e log p_{v_e},  n_doc[d] = N_d  -- the per-document sums of mmm_mixture_loglik, same expressions, same order;
+ *   total[0] = sum_d ll_doc / sum_d n_doc, total[1] = sum_d ll_doc, total[2] = sum_d n_doc over the documents with N_d > 0: total[0] is
+ *              the value of mmm_mixture_loglik on the same arguments, bit for bit;
+ *   cos_doc[d] = (sum_e n_e p_{v_e}) / (sqrt(sum_e n_e^2) * sqrt(sum_{v < V} p_v^2)): the cosine between the document's counts and its
+ *              reconstruction N_d p.  Each of the three sums is 64 partial sums, partial l over the indices l, l + 64, ... ascending (entries
+ *              in CSR order, terms v in index order), combined as a butterfly: l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  0 where a norm
+ *              is 0 (an empty or all-zero document).  The entries of a document are taken as given: duplicate terms are NOT merged (each
+ *              entry is a coordinate of its own in the numerator and in sum n_e^2);
+ *   total[3] = the mean of cos_doc over the documents with N_d > 0, by the 256 strided partial sums and the tree of total[0].
+ * No document with N_d > 0: total[0] and total[3] are NaN (0 / 0), as with mmm_mixture_loglik.  ll_doc, n_doc, cos_doc ([D] each) may be
+ * NULL.  MMM_ERR_ARG as mmm_mixture_loglik. */
+int mmm_mixture_score(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count,
+                      const double* props, const double* phi, double* ll_doc, double* n_doc, double* cos_doc, double* total /* [4] */);
+/* The same for every replica of a handle (R = mmm_lda_replicas; an ordinary handle is one replica) on a corpus of the caller's with the
+ * handle's D documents and terms < V (doc_ptr holds D + 1 offsets), read where the tables lie: replica r's outputs equal those of
+ * mmm_mixture_score on the theta and beta that mmm_lda_get returns after mmm_lda_select(r), bit for bit (theta = gamma / sum gamma is formed
+ * in the kernel from the gamma of the replica's own pass).  total [R][4]; ll_doc, cos_doc [R][D], may be NULL.  One upload (the corpus), two
+ * launches, one download, whatever R.  The handle is left as it was, its selected replica included.
+ * MMM_ERR_UNSUPPORTED: ILDA handles; MMM_ERR_ARG: a replica on which no pass has run, a corpus that is no CSR of terms < V. */
+int mmm_lda_score_replicas(mmm_lda* m, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, double* total, double* ll_doc,
+                           double* cos_doc);
+
 #ifdef __cplusplus
 }
 #endif

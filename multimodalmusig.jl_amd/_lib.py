@@ -141,6 +141,9 @@ _SIGS = {
     "mmm_ctm_match_replicas": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     "mmm_lda_replica_consensus": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_ctm_replica_consensus": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_split_counts": (C.c_int, [vp, C.c_int, i64p, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]),
+    "mmm_mixture_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, f64p, vp, vp, vp, f64p]),
+    "mmm_lda_score_replicas": (C.c_int, [vp, i64p, vp, vp, f64p, vp, vp]),
 }
 
 

@@ -5,21 +5,9 @@
 // kernels restate are in include/mmmusig.h and DESIGN.md ("Bootstrap of the exposures").  Everything here is integer arithmetic or a
 // fixed-order double sum: the same arguments give the same bits on every run and every launch geometry.
 #include "mmm_internal.h"
+#include "mmm_philox.h"
 
 namespace {
-
-// ---- Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11) -----------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t u[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    u[0] = c0; u[1] = c1; u[2] = c2; u[3] = c3;
-}
 
 constexpr int kRsWaves = 4;        // waves per block; each takes one replicate of the block's document at a time
 constexpr int kRsMaxW = 2048;      // longest row kept in LDS: 4 B x 2048 x (1 prefix row + kRsWaves histograms) = 40 KiB per block at most;

@@ -10,6 +10,19 @@
 #include "dev_math.h"
 #include "mmm_arith.h"
 
+// the CSR arrays of a caller (mmm_internal.h): offsets from 0 and not decreasing, terms in [0, V), counts >= 0
+int mmm_check_csr(mmm_ctx* ctx, const char* who, int D, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count)
+{
+    MMM_CHECK(ctx, D >= 0 && doc_ptr, "%s: D < 0 or doc_ptr == NULL", who);
+    MMM_CHECK(ctx, doc_ptr[0] == 0, "%s: doc_ptr[0] != 0", who);
+    for (int d = 0; d < D; ++d) MMM_CHECK(ctx, doc_ptr[d + 1] >= doc_ptr[d], "%s: doc_ptr decreases at document %d", who, d);
+    const int64_t nnz = doc_ptr[D];
+    MMM_CHECK(ctx, nnz == 0 || (term && count), "%s: NULL term / count", who);
+    for (int64_t e = 0; e < nnz; ++e)
+        MMM_CHECK(ctx, term[e] >= 0 && term[e] < V && count[e] >= 0, "%s: entry %lld has term %d (V = %d), count %d", who, (long long)e, term[e], V, count[e]);
+    return MMM_OK;
+}
+
 namespace {
 
 // mode 0: λ_objective(x = λ, other = ν, c = Ndivζ, sumθ, μ, S = invΣ);  mode 1: ν_objective(x = ν, other = λ, c, μ unused, S)
@@ -106,18 +119,6 @@ __global__ __launch_bounds__(256) void k_free_loglik_total(int D, const double* 
     if (threadIdx.x == 0) { out[0] = sh[0][0] / sh[1][0]; out[1] = sh[0][0]; out[2] = sh[1][0]; }
 }
 
-int check_csr(mmm_ctx* ctx, const char* who, int D, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count)
-{
-    MMM_CHECK(ctx, D >= 0 && doc_ptr, "%s: D < 0 or doc_ptr == NULL", who);
-    MMM_CHECK(ctx, doc_ptr[0] == 0, "%s: doc_ptr[0] != 0", who);
-    for (int d = 0; d < D; ++d) MMM_CHECK(ctx, doc_ptr[d + 1] >= doc_ptr[d], "%s: doc_ptr decreases at document %d", who, d);
-    const int64_t nnz = doc_ptr[D];
-    MMM_CHECK(ctx, nnz == 0 || (term && count), "%s: NULL term / count", who);
-    for (int64_t e = 0; e < nnz; ++e)
-        MMM_CHECK(ctx, term[e] >= 0 && term[e] < V && count[e] >= 0, "%s: entry %lld has term %d (V = %d), count %d", who, (long long)e, term[e], V, count[e]);
-    return MMM_OK;
-}
-
 // device copies of the CSR arrays + log-likelihood from device-resident props [K x D] and phi [k V + v]
 int loglik_from_tables(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* props_dev,
                        const double* phi_dev, double* ll)
@@ -203,7 +204,7 @@ int mmm_mixture_loglik(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr
     if (!ctx) return MMM_ERR_ARG;
     MMM_HIP(ctx, hipSetDevice(ctx->device));
     MMM_CHECK(ctx, K >= 1 && V >= 1 && props && phi && ll, "mmm_mixture_loglik: NULL argument, K < 1 or V < 1");
-    if (int rc = check_csr(ctx, "mmm_mixture_loglik", D, V, doc_ptr, term, count)) return rc;
+    if (int rc = mmm_check_csr(ctx, "mmm_mixture_loglik", D, V, doc_ptr, term, count)) return rc;
     DevBuf<double> p, f;
     MMM_HIP(ctx, p.alloc((size_t)K * D)); MMM_HIP(ctx, f.alloc((size_t)K * V));
     if (D) MMM_HIP(ctx, hipMemcpyAsync(p.p, props, sizeof(double) * K * D, hipMemcpyHostToDevice, ctx->stream));
@@ -217,7 +218,7 @@ int mmm_mixture_loglik_features(mmm_ctx* ctx, int D, int K, int V, int I, const 
     if (!ctx) return MMM_ERR_ARG;
     MMM_HIP(ctx, hipSetDevice(ctx->device));
     MMM_CHECK(ctx, K >= 1 && V >= 1 && I >= 1 && J && features && eta && phi && ll, "mmm_mixture_loglik_features: NULL argument, K < 1, V < 1 or I < 1");
-    if (int rc = check_csr(ctx, "mmm_mixture_loglik_features", D, V, doc_ptr, term, count)) return rc;
+    if (int rc = mmm_check_csr(ctx, "mmm_mixture_loglik_features", D, V, doc_ptr, term, count)) return rc;
     std::vector<int> joff((size_t)I + 1, 0);
     for (int i = 0; i < I; ++i) { MMM_CHECK(ctx, J[i] >= 1, "mmm_mixture_loglik_features: J[%d] < 1", i); joff[i + 1] = joff[i] + J[i]; }
     for (int i = 0; i < I; ++i)

@@ -1713,4 +1713,25 @@ int mmm_lda_replica_consensus(mmm_lda* m, int ref, int nq, const double* q, int3
                                 sd, quant);
 }
 
+// ---- every replica scored on a corpus of the caller's where its tables lie (select.hip; include/mmmusig.h) -----------------------------------
+// The gamma and beta of replica r in the ring slot of ITS pass, as lda_replica_tables picks lambda; theta is formed from gamma in the kernel.
+int mmm_lda_score_replicas(mmm_lda* m, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, double* total, double* ll_doc, double* cos_doc)
+{
+    if (!m) return MMM_ERR_ARG;
+    int rc = prepare_call(m);
+    if (rc) return rc;
+    if (m->ilda) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_score_replicas: the topics of an ILDA handle are factorised over the features; score its "
+                                 "downloaded tables with mmm_mixture_loglik_features");
+    if (m->R > 1) { m->rep_t[(size_t)m->sel] = m->t; m->rep_hist[(size_t)m->sel] = m->n_hist; }
+    std::vector<const double*> gam((size_t)m->R), bet((size_t)m->R);
+    for (int r = 0; r < m->R; ++r) {
+        const int t = m->R > 1 ? m->rep_t[(size_t)r] : m->t;
+        MMM_CHECK(m->ctx, t > 0, "mmm_lda_score_replicas: no pass has run on replica %d (fit the handle first)", r);
+        gam[(size_t)r] = m->gamma[t % 3].p + (size_t)r * m->K * m->D;
+        bet[(size_t)r] = m->beta[t % 3].p + (size_t)r * m->V * m->K;
+    }
+    return mmm_score_tables(m->ctx, "mmm_lda_score_replicas", m->R, m->D, m->K, m->V, doc_ptr, term, count, gam.data(), bet.data(), true, total, ll_doc, nullptr,
+                            cos_doc);
+}
+
 } // extern "C"

@@ -225,3 +225,13 @@ int mmm_match_tables(mmm_ctx* ctx, const char* who, int R, int K, int C, int V, 
                      int32_t* assign, double* matched);
 int mmm_consensus_tables(mmm_ctx* ctx, const char* who, int R, int K, int V, const double* const* h_tab, size_t sk, size_t sv, int ref, int nq, const double* q,
                          int32_t* assign, double* matched, double* stability, double* mean, double* sd, double* quant);
+
+// ---- caller CSR arrays (free.hip): doc_ptr from 0 and not decreasing, terms in [0, V), counts >= 0; MMM_ERR_ARG with `who` in the message
+int mmm_check_csr(mmm_ctx* ctx, const char* who, int D, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count);
+
+// ---- held-out score (select.hip) for mmm_mixture_score and the handle entry of lda.hip.  R replicas; the CSR is the caller's (host, checked here).
+// h_prop[r]: device pointer of replica r's K x D table -- proportions, or with from_gamma the gamma the proportions are formed from
+// (theta = gamma / sum gamma, the expression of the mmm_lda_get(THETA) route); h_phi[r]: device pointer of its [k V + v] table.
+// Host outputs total [R][4], ll_doc / n_doc / cos_doc [R][D] (each may be NULL); waits for the device.
+int mmm_score_tables(mmm_ctx* ctx, const char* who, int R, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count,
+                     const double* const* h_prop, const double* const* h_phi, bool from_gamma, double* total, double* ll_doc, double* n_doc, double* cos_doc);

@@ -413,8 +413,19 @@ function calculate_loglikelihood(X::Vector{Matrix{Int}}, θ::Matrix{Float64}, β
                 ctx.h, length(X), K, V, doc_ptr, term, count, vec(θ), vec(β), ll), ctx, "mmm_mixture_loglik")
     return ll[]
 end
+# score_exposures(X, θ, β) -- no counterpart upstream (include/mmmusig.h, mmm_mixture_score): per document the log-likelihood, the number of
+# mutations and the cosine between the counts and their reconstruction; ll equals calculate_loglikelihood(X, θ, β) bit for bit
+function score_exposures(X::Vector{Matrix{Int}}, θ::Matrix{Float64}, β::Matrix{Float64}; ctx::Context=default_context())
+    doc_ptr, term, count = pack_lda(X)
+    D, K, V = length(X), size(θ, 1), size(β, 1)
+    ll_doc = zeros(Float64, D); n_doc = zeros(Float64, D); cos_doc = zeros(Float64, D); total = zeros(Float64, 4)
+    check(ccall((:mmm_mixture_score, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                ctx.h, D, K, V, doc_ptr, term, count, vec(θ), vec(β), ll_doc, n_doc, cos_doc, total), ctx, "mmm_mixture_score")
+    return (ll=total[1], ll_doc=ll_doc, n_doc=n_doc, cosine_doc=cos_doc, cosine=total[4])
+end
 calculate_loglikelihood(X::Vector{Matrix{Int}}, model::LDA) = calculate_loglikelihood(X, model.θ, model.β; ctx=model.ctx)
-calculate_loglikelihood(model::LDA) = calculate_loglikelihood(model.X, model.θ, model.β; ctx=model.ctx)
+calculate_loglikelihood(model::LDA) =calculate_loglikelihood(model.X, model.θ, model.β; ctx=model.ctx)
 
 function calculate_loglikelihood(X::Vector{Matrix{Int}}, features::Matrix{Int}, θ::Matrix{Float64}, β::Vector{Matrix{Float64}};
                                  ctx::Context=default_context())

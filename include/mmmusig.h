@@ -95,7 +95,8 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_CTM_PIPE_GAUSS = 1 << 12,    /* Gaussian M-step: the three-barrier-per-column inversion instead of the pipelined one (sum K <= 32); same bits         */
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
     MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
-    MMM_OFF_ALL = (1 << 15) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
+    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures: read the catalogue through L2 even where it fits LDS; same bits                                           */
+    MMM_OFF_ALL = (1 << 16) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
 typedef struct {
     int lda_build;        /* MMM_BUILD_*: E-step build of LDA / ILDA handles                                                              */
@@ -524,6 +525,35 @@ int mmm_mixture_score(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr,
  * MMM_ERR_UNSUPPORTED: ILDA handles; MMM_ERR_ARG: a replica on which no pass has run, a corpus that is no CSR of terms < V. */
 int mmm_lda_score_replicas(mmm_lda* m, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, double* total, double* ll_doc,
                            double* cos_doc);
+
+/* ---- exposures to a FIXED catalogue of signatures, with sparse selection (signature assignment / refitting; no counterpart in the reference,
+ * DESIGN.md section 4.13).  CSR corpus as mmm_mixture_score takes it; cat [C][V], >= 0, finite, every row sum > 0 (rows need not be
+ * normalised); allowed [D][C] (non-zero: the signature may be used) or NULL = all; penalty [D] or NULL = no elimination.
+ * Per document d.  n_v: the dense count vector (duplicate terms summed), N = sum_v n_v, f_v = n_v / N; P[c][v] = cat[c][v] / sum_v cat[c][v]
+ * (the sum in index order).
+ * fit(A), A a set of signatures: w_c = 1 / |A| on A, 0 elsewhere (every fit is a cold start: fit(A) depends on A alone, not on the path to
+ *   A); iterations t = 1 .. maxiter:  q_v = sum_c w_c P[c][v];  r_v = f_v / q_v where n_v > 0 and q_v > 0, else 0;  g_c = sum_v r_v P[c][v];
+ *   w'_c = w_c g_c;  stop after an iteration with max_c |w'_c - w_c| < tol (strict: tol = 0 runs maxiter iterations).  Then, with
+ *   S = sum_c w_c:  w <- w / S if S > 0 (S = 0: A produces none of the document's mutations and w stays 0);  q recomputed;
+ *   ll(A) = sum over n_v > 0, q_v > 0 of n_v log q_v;  u(A) = sum over n_v > 0, q_v = 0 of n_v -- the mutations no signature of A can produce.
+ * Order of the sums: q_v and S sequentially over c ascending; g_c and ll as 64 partial sums, partial l over the indices l, l + 64, ...
+ *   ascending, combined by the butterfly of mmm_mixture_score's cosine sums (l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1).  Products, sums
+ *   and the (IEEE, correctly rounded) divisions are separate roundings.  All terms are >= 0, so a zero weight or a zero r_v may be added or
+ *   left out without changing a bit.  log is the device library's (< 1 ulp); it enters ll and cost only.
+ * Elimination: A = {c : allowed[d][c]}; fit(A).  With a penalty, while |A| > 1: c* = the member of A with the smallest w_c (ties: the lowest
+ *   c); B = A \ {c*}; fit(B); delta = ll(A) - ll(B) if u(B) == u(A), else +inf; if delta < penalty[d]: order[d][j] = c*, cost[d][j] = delta
+ *   for round j = 0, 1, ..., and A <- B with B's w and ll; otherwise stop.  (Smallest contribution first: one refit per round, and the choice
+ *   is made on values that only +, x, / and comparisons decide.)
+ * Outputs: w[d][.] the final weights (exactly 0 outside A), active[d][c] = 1 on A, order / cost (rounds that did not run: -1 / 0),
+ *   ll_doc = ll(A), unexplained = u(A), iters = the EM iterations of all fits of the document.  N = 0 or an empty `allowed` row: all outputs 0,
+ *   order -1, unexplained = N.  Every output except w may be NULL.  The same arguments give the same bits on every run, whatever D and
+ *   wherever the catalogue is held (LDS, or read through L2 when C V doubles exceed 96 KiB).
+ * Limits: 1 <= C <= 256, V >= 1 (C V < 2^31), D >= 0 (D = 0 writes nothing).  MMM_ERR_ARG: NULL pointers, a catalogue entry that is negative or
+ *   not finite, a catalogue row whose sum is 0, a penalty that is negative or not finite, maxiter < 1, tol < 0, a corpus that is no CSR of
+ *   terms < V.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_refit_exposures(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                        const uint8_t* allowed, const double* penalty, int maxiter, double tol, double* w, uint8_t* active, int32_t* order, double* cost,
+                        double* ll_doc, double* unexplained, int64_t* iters);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,349 @@
+// refit.hip -- mmm_refit_exposures: exposures of every document to a FIXED catalogue of signatures, with backward elimination per document
+// (no counterpart in the reference; include/mmmusig.h has the normative definition, DESIGN.md section 4.13 the reasoning).
+//
+// One wave per document, documents handed out through a work counter (a document with many active signatures runs up to C - 1 refits, one
+// with a one-signature `allowed` row runs one: a static deal would leave the launch waiting for its slowest wave).  All rounds of a document
+// run here; the host sees the final state only.  Lane l owns the terms v = l, l + 64, ...: the mixture q_v = sum_c w_c P[c][v] is a loop over
+// the active signatures per lane, the 64 partial sums of g_c = sum_v r_v P[c][v] are the lanes' own, and the butterfly that combines them
+// (l ^ 32, ^ 16, ..., ^ 1) is taken for up to 32 signatures at once as a TRANSPOSING reduction: at the step `off` a lane keeps half of its
+// registers and hands the other half to lane l ^ off, so the same pairs are added in the same order (addition commutes: same bits) with 32
+// exchanges for 32 signatures instead of 192, and lane l ends with the total of signature l >> 1.  The two widest steps are gfx950's row
+// swaps (v_permlane32_swap / v_permlane16_swap: the exchange and the select in one instruction pair).  64 signatures at once would save one
+// exchange in 64 and spill: 128 accumulator registers and 64 row offsets.
+#include "mmm_internal.h"
+#include "dev_math.h"
+
+namespace {
+
+constexpr int kRfMaxC = 256;
+constexpr int kRfMaxWaves = 8;                  // 8 waves of up to 256 VGPRs fill a CU: two per SIMD
+constexpr size_t kRfLdsBlock = 160 * 1024;      // LDS a block may take (the CU's)
+constexpr size_t kRfLdsP = 96 * 1024;           // the normalised catalogue is staged in LDS up to this size, read through L2 beyond
+
+struct RfArgs {
+    int D, C, V, Cp, maxiter;
+    double tol;
+    const int64_t* doc_ptr; const int32_t* term; const int32_t* count;
+    const double* P;                 // [C][V], rows normalised
+    const uint8_t* allowed;          // [D][C] or NULL
+    const double* penalty;           // [D] or NULL
+    double* w; uint8_t* active; int32_t* order; double* cost; double* ll; double* unex; long long* iters;      // order / cost may be NULL
+    int* counter;                    // next document
+    double* ws;                      // per wave 3 V doubles when they do not fit LDS
+};
+
+__device__ __forceinline__ void rf_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// g[j], j < 2^LOG: this lane's partial sums of 2^LOG signatures.  Returns, in lane l, the butterfly total (l ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1) of
+// signature j = l >> (6 - LOG): LOG transposing steps, then 6 - LOG plain ones.
+template <int LOG, int S>
+__device__ __forceinline__ void rf_transpose_steps(double (&g)[1 << LOG], int lane)
+{
+    if constexpr (S < LOG) {
+        constexpr int h = (1 << LOG) >> (S + 1), off = 32 >> S;
+        if constexpr (off >= 16) {
+#pragma unroll
+            for (int i = 0; i < h; ++i) {
+                // x = g[i], y = g[i + h]: after the swap the lanes without bit `off` hold (own g[i], partner's g[i]), the lanes with it
+                // (partner's g[i + h], own g[i + h])
+                const unsigned xl = (unsigned)__double2loint(g[i]), xh = (unsigned)__double2hiint(g[i]);
+                const unsigned yl = (unsigned)__double2loint(g[i + h]), yh = (unsigned)__double2hiint(g[i + h]);
+                const mmm_u2 a = off == 32 ? __builtin_amdgcn_permlane32_swap(xl, yl, false, false) : __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
+                const mmm_u2 b = off == 32 ? __builtin_amdgcn_permlane32_swap(xh, yh, false, false) : __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
+                g[i] = __hiloint2double((int)b.x, (int)a.x) + __hiloint2double((int)b.y, (int)a.y);
+            }
+        } else {
+            const bool up = (lane & off) != 0;
+#pragma unroll
+            for (int i = 0; i < h; ++i) {
+                const double send = up ? g[i] : g[i + h];
+                const double keep = up ? g[i + h] : g[i];
+                g[i] = keep + __shfl_xor(send, off, 64);
+            }
+        }
+        rf_transpose_steps<LOG, S + 1>(g, lane);
+    }
+}
+
+template <int LOG>
+__device__ __forceinline__ double rf_reduce(double (&g)[1 << LOG], int lane)
+{
+    rf_transpose_steps<LOG, 0>(g, lane);
+    double v = g[0];
+#pragma unroll
+    for (int s = LOG; s < 6; ++s) v += __shfl_xor(v, 32 >> s, 64);
+    return v;
+}
+
+// the totals g_c of the 2^LOG signatures act[0 .. 2^LOG) (padded with a valid row): per lane the terms v = lane, lane + 64, ... ascending
+template <int LOG>
+__device__ __forceinline__ double rf_gchunk(const double* __restrict__ P, const int* __restrict__ act, const double* __restrict__ r, int V, int lane)
+{
+    constexpr int W = 1 << LOG;
+    double g[W];
+    int row[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) { g[j] = 0.0; row[j] = act[j] * V; }
+    for (int v = lane; v < V; v += 64) {
+        const double rv = r[v];
+#pragma unroll
+        for (int j = 0; j < W; ++j) g[j] += rv * P[row[j] + v];
+    }
+    return rf_reduce<LOG>(g, lane);
+}
+
+template <bool P_LDS, bool F_LDS>
+__global__ __launch_bounds__(64 * kRfMaxWaves) void k_refit(const RfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_rf[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6);
+    const int C = a.C, V = a.V, Cp = a.Cp;
+    if (P_LDS) {
+        for (int i = tid; i < C * V; i += (int)blockDim.x) s_rf[i] = a.P[i];
+        __syncthreads();
+    }
+    const double* __restrict__ P = P_LDS ? s_rf : a.P;
+    // per wave: two weight vectors and two lists of active signatures (in the order of c, padded to a multiple of 64 with a valid row whose results are dropped),
+    // then n_v, f_v, r_v
+    double* base = s_rf + (P_LDS ? (size_t)C * V : 0) + (size_t)wave * (3 * (size_t)Cp + (F_LDS ? 3 * (size_t)V : 0));
+    double* wA = base;
+    double* wB = base + Cp;
+    int* actA = (int*)(base + 2 * (size_t)Cp);
+    int* actB = actA + Cp;
+    double* nb = F_LDS ? base + 3 * (size_t)Cp : a.ws + ((size_t)blockIdx.x * nw + wave) * 3 * (size_t)V;
+    double* fb = nb + V;
+    double* rb = fb + V;
+
+    for (;;) {
+        int d = 0;
+        if (lane == 0) d = atomicAdd(a.counter, 1);
+        d = __shfl(d, 0, 64);
+        if (d >= a.D) break;
+        // ---- n_v (duplicate terms summed: integer-valued doubles, exact in any order), N, f_v
+        for (int v = lane; v < V; v += 64) rb[v] = 0.0;
+        if (F_LDS) rf_wave_sync(); else __threadfence();
+        double Np = 0.0;
+        for (int64_t e = a.doc_ptr[d] + lane; e < a.doc_ptr[d + 1]; e += 64) {
+            const int cnt = a.count[e];
+            if (cnt > 0) { atomicAdd(&rb[a.term[e]], (double)cnt); Np += (double)cnt; }
+        }
+        const double N = wave_sum(Np);
+        if (F_LDS) rf_wave_sync(); else __threadfence();
+        for (int v = lane; v < V; v += 64) {
+            const double nv = rb[v];
+            nb[v] = nv;
+            fb[v] = N > 0.0 ? nv / N : 0.0;
+        }
+        // ---- A0
+        int n = 0;
+        for (int c0 = 0; c0 < C; c0 += 64) {
+            const int c = c0 + lane;
+            const bool on = c < C && (a.allowed ? a.allowed[(size_t)d * C + c] != 0 : true);
+            const unsigned long long m = __ballot(on);
+            if (on) actA[n + __popcll(m & ((1ull << lane) - 1ull))] = c;
+            n += __popcll(m);
+        }
+        rf_wave_sync();
+        if (N == 0.0 || n == 0) {
+            if (lane == 0) a.unex[d] = N;       // everything else keeps the zeros (order: -1) the host has put there
+            continue;
+        }
+        for (int i = n + lane; i < ((n + 63) & ~63); i += 64) actA[i] = actA[0];
+        const double pen = a.penalty ? a.penalty[d] : 0.0;
+        double llA = 0.0, uA = 0.0;
+        long long iters = 0;
+        int round = 0, drop = 0;
+        bool first = true;
+        // candidate = the set whose fit runs next: A0 first, then A without its smallest weight
+        double* cw = wA; int* cact = actA; int cn = n;
+        for (;;) {
+            // ---- fit(candidate): cold start
+            const double w0 = 1.0 / (double)cn;
+            for (int i = lane; i < cn; i += 64) cw[i] = w0;
+            rf_wave_sync();
+            int it = 0;
+            while (it < a.maxiter) {
+                ++it;
+                // two of the lane's terms at a time: their sums over c are independent chains (each still in the order of c)
+                for (int v = lane; v < V; v += 128) {
+                    const bool two = v + 64 < V;
+                    const int v1 = two ? v + 64 : v;
+                    double q = 0.0, q1 = 0.0;
+#pragma unroll 4
+                    for (int i = 0; i < cn; ++i) {
+                        const double wi = cw[i];
+                        const int row = cact[i] * V;
+                        q += wi * P[row + v];
+                        q1 += wi * P[row + v1];
+                    }
+                    rb[v] = (nb[v] > 0.0 && q > 0.0) ? fb[v] / q : 0.0;
+                    if (two) rb[v1] = (nb[v1] > 0.0 && q1 > 0.0) ? fb[v1] / q1 : 0.0;
+                }
+                rf_wave_sync();
+                double md = 0.0;
+                for (int b = 0; b < cn; b += 32) {
+                    const int m = min(32, cn - b);
+                    double g; int j;
+                    if (m <= 4) { g = rf_gchunk<2>(P, cact + b, rb, V, lane); j = lane >> 4; }
+                    else if (m <= 8) { g = rf_gchunk<3>(P, cact + b, rb, V, lane); j = lane >> 3; }
+                    else if (m <= 16) { g = rf_gchunk<4>(P, cact + b, rb, V, lane); j = lane >> 2; }
+                    else { g = rf_gchunk<5>(P, cact + b, rb, V, lane); j = lane >> 1; }
+                    if (j < m) {
+                        const double wo = cw[b + j], wn = wo * g;
+                        md = fmax(md, fabs(wn - wo));
+                        cw[b + j] = wn;           // the lanes that share j write the same bits
+                    }
+                }
+                rf_wave_sync();
+                if (wave_max(md) < a.tol) break;
+            }
+            iters += it;
+            double S = 0.0;
+            for (int i = 0; i < cn; ++i) S += cw[i];
+            rf_wave_sync();
+            if (S > 0.0)
+                for (int i = lane; i < cn; i += 64) cw[i] = cw[i] / S;
+            rf_wave_sync();
+            double lp = 0.0, up = 0.0;
+            for (int v = lane; v < V; v += 64) {
+                double q = 0.0;
+                for (int i = 0; i < cn; ++i) q += cw[i] * P[cact[i] * V + v];
+                const double nv = nb[v];
+                if (nv > 0.0) { if (q > 0.0) lp += nv * log(q); else up += nv; }
+            }
+            const double llB = wave_sum(lp), uB = wave_sum(up);
+            // ---- decide
+            if (first) { first = false; llA = llB; uA = uB; }
+            else {
+                const double delta = uB == uA ? llA - llB : __builtin_inf();
+                if (!(delta < pen)) break;
+                if (lane == 0) {
+                    if (a.order) a.order[(size_t)d * C + round] = actA[drop];
+                    if (a.cost) a.cost[(size_t)d * C + round] = delta;
+                }
+                ++round;
+                double* tw = wA; wA = wB; wB = tw;
+                int* ta = actA; actA = actB; actB = ta;
+                llA = llB; n = cn;
+            }
+            if (!a.penalty || n <= 1) break;
+            // ---- the member with the smallest weight, ties to the lowest c (the list is in the order of c)
+            double bv = __builtin_inf(); int bi = 0x7fffffff;
+            for (int i = lane; i < n; i += 64) { const double x = wA[i]; if (x < bv) { bv = x; bi = i; } }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ov = __shfl_xor(bv, off, 64); const int oi = __shfl_xor(bi, off, 64);
+                if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            drop = bi;
+            cn = n - 1;
+            for (int i = lane; i < cn; i += 64) actB[i] = actA[i < drop ? i : i + 1];
+            rf_wave_sync();
+            for (int i = cn + lane; i < ((cn + 63) & ~63); i += 64) actB[i] = actB[0];
+            cw = wB; cact = actB;
+        }
+        for (int i = lane; i < n; i += 64) {
+            a.w[(size_t)d * C + actA[i]] = wA[i];
+            a.active[(size_t)d * C + actA[i]] = 1;
+        }
+        if (lane == 0) { a.ll[d] = llA; a.unex[d] = uA; a.iters[d] = iters; }
+        rf_wave_sync();
+    }
+}
+
+} // namespace
+
+extern "C" int mmm_refit_exposures(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                                   const uint8_t* allowed, const double* penalty, int maxiter, double tol, double* w, uint8_t* active, int32_t* order, double* cost,
+                                   double* ll_doc, double* unexplained, int64_t* iters)
+{
+    if (!ctx) return MMM_ERR_ARG;
+    MMM_HIP(ctx, hipSetDevice(ctx->device));
+    MMM_CHECK(ctx, C >= 1 && V >= 1 && D >= 0 && cat && (D == 0 || w), "mmm_refit_exposures: NULL argument, D < 0, C < 1 or V < 1");
+    if (C > kRfMaxC) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_refit_exposures: C = %d catalogue signatures (limit %d)", C, kRfMaxC);
+    MMM_CHECK(ctx, maxiter >= 1 && tol >= 0.0, "mmm_refit_exposures: maxiter = %d (>= 1), tol = %g (>= 0)", maxiter, tol);
+    if ((size_t)C * (size_t)V >= ((size_t)1 << 31)) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_refit_exposures: C V = %zu (limit 2^31 - 1)", (size_t)C * V);
+    if (int rc = mmm_check_csr(ctx, "mmm_refit_exposures", D, V, doc_ptr, term, count)) return rc;
+    // P[c][v] = cat[c][v] / sum_v cat[c][v], the sum in index order
+    std::vector<double> P((size_t)C * V);
+    for (int c = 0; c < C; ++c) {
+        double s = 0.0;
+        for (int v = 0; v < V; ++v) {
+            const double x = cat[(size_t)c * V + v];
+            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "mmm_refit_exposures: catalogue entry (%d, %d) is negative or not finite", c, v);
+            s += x;
+        }
+        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "mmm_refit_exposures: catalogue row %d sums to %g", c, s);
+        for (int v = 0; v < V; ++v) P[(size_t)c * V + v] = cat[(size_t)c * V + v] / s;
+    }
+    if (penalty)
+        for (int d = 0; d < D; ++d) MMM_CHECK(ctx, std::isfinite(penalty[d]) && penalty[d] >= 0.0, "mmm_refit_exposures: penalty[%d] is negative or not finite", d);
+    if (D == 0) return MMM_OK;
+    const int64_t nnz = doc_ptr[D];
+    const size_t DC = (size_t)D * C;
+
+    // launch geometry: the catalogue in LDS when it fits, as many waves per block as the per-wave buffers leave room for
+    const int Cp = (C + 63) & ~63;
+    const size_t p_bytes = sizeof(double) * (size_t)C * V, small = sizeof(double) * 3 * (size_t)Cp, big = small + sizeof(double) * 3 * (size_t)V;
+    bool p_lds = p_bytes <= kRfLdsP && !mmm_off(ctx->tune, MMM_OFF_REFIT_LDS), f_lds = true;
+    int nw = 0;
+    for (int pass = 0; pass < 2 && !nw; ++pass) {
+        for (int t = kRfMaxWaves; t >= 1 && !nw; t >>= 1)
+            if ((p_lds ? p_bytes : 0) + t * big <= kRfLdsBlock) nw = t;
+        if (!nw) { if (p_lds) p_lds = false; else break; }
+    }
+    if (!nw) { f_lds = false; nw = kRfMaxWaves; }
+    // few documents: fewer waves per block, so that they spread over the CUs (a wave alone on its SIMD runs its latency chain fastest)
+    const int cus = std::max(1, ctx->num_cu);
+    while (nw > 1 && ((int64_t)D + nw - 1) / nw < cus) nw >>= 1;
+    const size_t lds = (p_lds ? p_bytes : 0) + nw * (f_lds ? big : small);
+    // blocks a CU holds at once: by waves (8 of this kernel's register budget) and by the LDS a block takes
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kRfMaxWaves / nw, (int64_t)(kRfLdsBlock / lds)));
+    const int64_t want = ((int64_t)D + nw - 1) / nw, resident = (int64_t)cus * per_cu;
+    const unsigned grid = (unsigned)std::min(want, resident);
+
+    DevBuf<int64_t> dp; DevBuf<int32_t> tc, ord; DevBuf<double> Pd, pend, outd, ws; DevBuf<uint8_t> alw, act; DevBuf<int> counter;
+    MMM_HIP(ctx, dp.alloc((size_t)D + 1 + D)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, Pd.alloc(P.size()));
+    MMM_HIP(ctx, outd.alloc(DC + (cost ? DC : 0) + 2 * (size_t)D)); MMM_HIP(ctx, act.alloc(DC)); MMM_HIP(ctx, counter.alloc(1));
+    if (order) MMM_HIP(ctx, ord.alloc(DC));
+    if (allowed) MMM_HIP(ctx, alw.alloc(DC));
+    if (penalty) MMM_HIP(ctx, pend.alloc((size_t)D));
+    if (!f_lds) MMM_HIP(ctx, ws.alloc((size_t)grid * nw * 3 * (size_t)V));
+    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz) {
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    MMM_HIP(ctx, hipMemcpyAsync(Pd.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (allowed) MMM_HIP(ctx, hipMemcpyAsync(alw.p, allowed, DC, hipMemcpyHostToDevice, ctx->stream));
+    if (penalty) MMM_HIP(ctx, hipMemcpyAsync(pend.p, penalty, sizeof(double) * (size_t)D, hipMemcpyHostToDevice, ctx->stream));
+    // what a document that never runs (N = 0, empty `allowed` row) and a round that never runs leave behind
+    MMM_HIP(ctx, hipMemsetAsync(outd.p, 0, sizeof(double) * outd.n, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(dp.p + D + 1, 0, sizeof(int64_t) * (size_t)D, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(act.p, 0, DC, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(counter.p, 0, sizeof(int), ctx->stream));
+    if (order) MMM_HIP(ctx, hipMemsetAsync(ord.p, 0xff, sizeof(int32_t) * DC, ctx->stream));
+
+    RfArgs a;
+    a.D = D; a.C = C; a.V = V; a.Cp = Cp; a.maxiter = maxiter; a.tol = tol;
+    a.doc_ptr = dp.p; a.term = tc.p; a.count = tc.p + nnz; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.penalty = penalty ? pend.p : nullptr;
+    a.w = outd.p; a.cost = cost ? outd.p + DC : nullptr; a.ll = outd.p + DC + (cost ? DC : 0); a.unex = a.ll + D;
+    a.active = act.p; a.order = order ? ord.p : nullptr; a.iters = (long long*)(dp.p + D + 1); a.counter = counter.p; a.ws = f_lds ? nullptr : ws.p;
+    auto kern = p_lds ? k_refit<true, true> : (f_lds ? k_refit<false, true> : k_refit<false, false>);
+    if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, ctx->stream, a);
+    MMM_LAUNCH_CHECK(ctx);
+    MMM_HIP(ctx, hipMemcpyAsync(w, a.w, sizeof(double) * DC, hipMemcpyDeviceToHost, ctx->stream));
+    if (cost) MMM_HIP(ctx, hipMemcpyAsync(cost, a.cost, sizeof(double) * DC, hipMemcpyDeviceToHost, ctx->stream));
+    if (ll_doc) MMM_HIP(ctx, hipMemcpyAsync(ll_doc, a.ll, sizeof(double) * (size_t)D, hipMemcpyDeviceToHost, ctx->stream));
+    if (unexplained) MMM_HIP(ctx, hipMemcpyAsync(unexplained, a.unex, sizeof(double) * (size_t)D, hipMemcpyDeviceToHost, ctx->stream));
+    if (active) MMM_HIP(ctx, hipMemcpyAsync(active, act.p, DC, hipMemcpyDeviceToHost, ctx->stream));
+    if (order) MMM_HIP(ctx, hipMemcpyAsync(order, ord.p, sizeof(int32_t) * DC, hipMemcpyDeviceToHost, ctx->stream));
+    if (iters) MMM_HIP(ctx, hipMemcpyAsync(iters, a.iters, sizeof(int64_t) * (size_t)D, hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MMM_OK;
+}

@@ -424,6 +424,27 @@ function score_exposures(X::Vector{Matrix{Int}}, θ::Matrix{Float64}, β::Matrix
                 ctx.h, D, K, V, doc_ptr, term, count, vec(θ), vec(β), ll_doc, n_doc, cos_doc, total), ctx, "mmm_mixture_score")
     return (ll=total[1], ll_doc=ll_doc, n_doc=n_doc, cosine_doc=cos_doc, cosine=total[4])
 end
+# refit_exposures(X, catalogue) -- no counterpart upstream (include/mmmusig.h, mmm_refit_exposures): the exposures of every sample to a FIXED
+# catalogue (C x V, one row per signature, rows need not be normalised), with backward elimination per sample.  penalty: :bic (0.5 log N_d), a
+# number, or nothing (no elimination); allowed: a C x D Bool matrix (column d: the signatures sample d may use) or nothing.  exposures and
+# active come back C x D; order (0-based catalogue rows, -1 padded) and cost C x D with one COLUMN per sample.
+function refit_exposures(X::Vector{Matrix{Int}}, catalogue::Matrix{Float64}; penalty=:bic, allowed::Union{Nothing,AbstractMatrix{Bool}}=nothing,
+                         maxiter::Integer=1000, tol::Real=1e-9, ctx::Context=default_context())
+    doc_ptr, term, count = pack_lda(X)
+    D, C, V = length(X), size(catalogue, 1), size(catalogue, 2)
+    N = Float64[sum(Float64, x[:, 2]) for x in X]
+    pen = penalty === nothing ? C_NULL : (penalty === :bic ? 0.5 .* log.(max.(N, 1.0)) : fill(Float64(penalty), D))
+    alw = allowed === nothing ? C_NULL : UInt8.(vec(allowed))
+    allowed === nothing || size(allowed) == (C, D) || throw(ArgumentError("allowed must be C x D"))
+    w = zeros(Float64, C, D); active = zeros(UInt8, C, D); order = fill(Int32(-1), C, D); cost = zeros(Float64, C, D)
+    ll_doc = zeros(Float64, D); unexplained = zeros(Float64, D); iters = zeros(Int64, D)
+    check(ccall((:mmm_refit_exposures, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cvoid},
+                 Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}),
+                ctx.h, D, C, V, doc_ptr, term, count, vec(permutedims(catalogue)), alw, pen, maxiter, tol, w, active, order, cost, ll_doc, unexplained, iters),
+          ctx, "mmm_refit_exposures")
+    return (exposures=w, active=active .!= 0, order=order, cost=cost, ll_doc=ll_doc, unexplained=unexplained, iters=iters, counts=w .* N')
+end
 calculate_loglikelihood(X::Vector{Matrix{Int}}, model::LDA) = calculate_loglikelihood(X, model.θ, model.β; ctx=model.ctx)
 calculate_loglikelihood(model::LDA) =calculate_loglikelihood(model.X, model.θ, model.β; ctx=model.ctx)
 

@@ -47,14 +47,17 @@ constexpr int kMaxWavesE = 12;                       // fused E-step kernel: up 
 
 struct LdaDev {
     int D, V, K;
-    const int64_t* doc_ptr;
+    int Vp;               // slots per row of `dense` / `dense16` (16 x slots per lane; 16-bit rows keep an even number of slots per lane).  Fourth of the
+                          // leading 16 bytes: the kernels fetch D .. alpha with one scalar load, and a padding word inside it is a register the
+                          // compiler reuses for an argument fetched later -- which makes that fetch wait for this one (lda_estep.cuh, start-up)
+    const int64_t* doc_ptr;      // [D + 1], never NULL and at least 16 bytes whatever form the kernels read (mmm_lda_create uploads it before any row form is
+                                 // built): lda_row_read's grouped loads use its first 8 bytes as the address of a lane that has nothing to fetch
     const int2* tc;
     double alpha, eta;
     const int2* ell;      // [D][V] rows padded with (-1, 0), or NULL: lets the ll blocks fetch a document's terms without first
                           // waiting for doc_ptr (built when V <= 128 and no document lists a term twice)
     const int* dense;     // [D][16][Vp / 16] rows of counts, LANE-major: the Vp / 16 slots of lane l (terms l, 16 + l, ...) are contiguous, so a lane
                           // requests its part of a row with one load (lda_rows.cuh); or NULL.  The ll blocks read these instead of ell
-    int Vp;               // slots per row (16 x slots per lane; 16-bit rows keep an even number of slots per lane)
     const unsigned short* dense16;   // the same rows as 16-bit counts (every count < 65536), or NULL: 2 bytes per term slot
 };
 
@@ -134,6 +137,12 @@ __device__ __forceinline__ double cells_wait_sum(const unsigned long long* c, in
     return v;
 }
 
+// ctl->stop, written by the previous launch's tail wave.  Requested as a vector load (a relaxed atomic load stays one) at the top of a kernel,
+// ahead of its other loads: vector loads return in order, so by the time anything else has arrived the flag has too, and the issue of no other
+// load waits for it (as a scalar load it sat in front of every kernel argument fetched after it).  lda_stop_now where the flag is consumed.
+__device__ __forceinline__ int lda_stop_request(const LdaCtl* ctl) { return __hip_atomic_load(&ctl->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ bool lda_stop_now(int requested) { return __builtin_amdgcn_readfirstlane(requested) != 0; }
+
 constexpr int kIldaMaxI = 8, kIldaMaxSJ = 512;
 
 struct EstepArgs {
@@ -147,6 +156,13 @@ struct EstepArgs {
     int pstride;       // row stride of a block's partial: V, or V rounded up to 16 for k_lda_reduce_ll_mstep (pad entries stay 0)
     const double* aexp; // single-step build: a = exp(Elntheta_t) [D][K], formed (with Elntheta_t) by the PREVIOUS pass's merged launch (its
                        // prologue blocks, k_lda_reduce_ll_mstep) -- the kernel then starts at the term phase; NULL: it forms them itself
+    // the ring slots of pass t, resolved by the host where t is known (launch_estep): k_lda_estep and k_lda_estep_block read these instead of
+    // forming t % 3 and fetching the pointers at computed offsets of the kernarg segment, a dependent scalar round before their first load
+    struct Slots { const double* gam; const double* gprev; double* gnext; double* Eln; const double* eB; const double* bprev; } now;
+    void resolve()
+    {
+        now = Slots{gamma.s[t % 3], gamma.s[(t + 2) % 3], gamma.s[(t + 1) % 3], Elntheta.s[t % 3], expElnbeta.s[(t + 2) % 3], beta.s[(t + 2) % 3]};
+    }
 };
 
 #ifdef MMM_DIAG_STAMPS
@@ -255,7 +271,7 @@ struct mmm_lda {
     int grid_e = 1, waves_e = 8, grid_s = 1;
     size_t lds_e = 0, lds_tab = 0;
     bool block_stats = false;   // single-step passes without the E-step ll take k_lda_estep_block (statistics as a block product, no slabs)
-    size_t lds_b = 0; bool attr_b = false;      // its dynamic LDS: table | r | a
+    size_t lds_b = 0; bool attr_b[2] = {false, false};      // its dynamic LDS: table | r | a
     // ILDA (src/ILDA.jl): feature-factorised topics; the V x K rings then hold the effective tables
     bool ilda = false;
     IldaDesc ids{};
@@ -267,7 +283,7 @@ struct mmm_lda {
     int R = 1, sel = 0;
     std::vector<int> rep_t, rep_hist;
     PinnedCtl pin;                      // fit_batch: in-stream snapshots of the R control blocks (two slots)
-    LdaDev dev() const { return LdaDev{D, V, K, doc_ptr.p, tc.p, alpha, eta, tc_ell.p, (drows && !cnt16.p) ? cnt_dense.p : nullptr, 16 * SLs, cnt16.p}; }
+    LdaDev dev() const { return LdaDev{D, V, K, 16 * SLs, doc_ptr.p, tc.p, alpha, eta, tc_ell.p, (drows && !cnt16.p) ? cnt_dense.p : nullptr, cnt16.p}; }
     int cur() const { return t % 3; }
     Ring ring(DevBuf<double>* b) const { return Ring{{b[0].p, b[1].p, b[2].p}}; }
     // the selected replica's slot s of a V x K ring / a K x D ring, its control block and ll history (R = 1: the arrays themselves)
@@ -351,8 +367,10 @@ template <int KPV, int VT, bool RB>
 int go_estep_block(mmm_lda* m, const EstepArgs& a)
 {
     mmm_ctx* ctx = m->ctx;
-    auto k = k_lda_estep_block<KPV, VT, RB>;
-    if (!m->attr_b) { int rc = set_lds(ctx, k, m->lds_b); if (rc) return rc; m->attr_b = true; }
+    // rows of 16-bit counts (a single fit's default corpus form) have a build of their own: its start-up loads leave in one group
+    const bool r16 = !RB && a.c.dense16 != nullptr;
+    auto k = r16 ? k_lda_estep_block<KPV, VT, RB, !RB> : k_lda_estep_block<KPV, VT, RB, false>;
+    if (!m->attr_b[r16]) { int rc = set_lds(ctx, k, m->lds_b); if (rc) return rc; m->attr_b[r16] = true; }
     hipLaunchKernelGGL(k, dim3(m->grid_e, RB ? m->R : 1), dim3(m->waves_e * MMM_WAVE), m->lds_b, ctx->stream, a);
     return MMM_OK;
 }
@@ -391,10 +409,12 @@ int dense_slots(int V) { return V <= 32 ? 2 : (V <= 48 ? 3 : (V <= 96 ? 6 : (V <
 
 // RB: a batched pass (split pipeline; the ll rides in the reduce launch, so a.do_ll = 0 and the wide path never comes here)
 template <bool RB = false>
-int launch_estep(mmm_lda* m, const EstepArgs& a)
+int launch_estep(mmm_lda* m, const EstepArgs& pass)
 {
     mmm_ctx* ctx = m->ctx;
     int rc = MMM_OK;
+    EstepArgs a = pass;
+    a.resolve();
     if (m->dense && !a.do_ll) {
         MMM_KP_SWITCH(m, {
             if constexpr (KPV >= 4 && KPV <= 16) {

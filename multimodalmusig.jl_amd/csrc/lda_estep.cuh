@@ -7,16 +7,16 @@ __device__ __forceinline__ void lds_wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
-// What k_lda_estep and k_lda_estep_block resolve first: the arrays of pass t in their ring slots (replica blockIdx.y's copies in a batch build,
-// rep()) and the block's partial statistics.  (k_lda_estep_dense and the wide kernels of lda_stage.cuh spell their four slots out: through
-// this struct the scalar instructions at their heads come out in another order, and those kernels are kept instruction for instruction.)
+// What k_lda_estep and k_lda_estep_block resolve first: the arrays of pass t (EstepArgs::now: the host has resolved the ring slots; replica
+// blockIdx.y's copies in a batch build, rep()) and the block's partial statistics.  (k_lda_estep_dense and the wide kernels of lda_stage.cuh
+// spell their four slots out: through this struct the scalar instructions at their heads come out in another order, and those kernels
+// are kept instruction for instruction.)
 template <bool RB = false>
 struct EstepPass {
     const double* __restrict__ gam; const double* __restrict__ gprev; double* __restrict__ gnext; double* __restrict__ Eln;
     const double* __restrict__ eB; const double* __restrict__ bprev;
     __device__ __forceinline__ explicit EstepPass(const EstepArgs& a)
-        : gam(a.gamma.s[a.t % 3]), gprev(a.gamma.s[(a.t + 2) % 3]), gnext(a.gamma.s[(a.t + 1) % 3]), Eln(a.Elntheta.s[a.t % 3]),
-          eB(a.expElnbeta.s[(a.t + 2) % 3]), bprev(a.beta.s[(a.t + 2) % 3])
+        : gam(a.now.gam), gprev(a.now.gprev), gnext(a.now.gnext), Eln(a.now.Eln), eB(a.now.eB), bprev(a.now.bprev)
     {
         if constexpr (RB) {
             const size_t KD = (size_t)a.c.K * a.c.D, VK = (size_t)a.c.V * a.c.K;
@@ -24,7 +24,10 @@ struct EstepPass {
             eB = rep<RB>(eB, VK); bprev = rep<RB>(bprev, VK);
         }
     }
-    static __device__ __forceinline__ int stop(const EstepArgs& a) { return rep<RB>(a.ctl, 1)->stop; }
+    // ctl->stop was written by the previous launch's tail wave: a trip to memory.  As a VECTOR load (a relaxed atomic load is not made a scalar
+    // one) issued ahead of the kernel's other loads it returns in order with them and no other load's issue waits for it -- scalar loads
+    // return out of order, so the wait for any kernel argument fetched after it was a wait for this flag.  stop_now() where it is consumed.
+    static __device__ __forceinline__ int stop_request(const EstepArgs& a) { return lda_stop_request(rep<RB>(a.ctl, 1)); }
     static __device__ __forceinline__ double* partial(const EstepArgs& a, const int K)
     {
         double* out = a.partial + (size_t)blockIdx.x * K * a.pstride;
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
     constexpr int G = MMM_WAVE / L;                   // documents per wave step
     constexpr int PRE = (96 + L - 1) / L;             // chunks prefetched into registers (covers a 96-term document)
     MMM_STAMP(0);
-    const int stop = EstepPass<RB>::stop(a);          // consumed after the first prologue (its latency is hidden)
+    const int stop = EstepPass<RB>::stop_request(a);  // consumed after the first prologue; a vector load ahead of every other (lda_stop_request)
     const EstepPass<RB> io(a);
     const int K = a.c.K, D = a.c.D;
     const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             nchmax = __builtin_amdgcn_readfirstlane(nchmax);
         }
         // first step: loads issued before the prologue math (later steps: requested a step ahead)
-        if (SINGLE || first) lda_row_read<L, PRE, true, true, true>(a.c, drows, rows, d, valid, l, V, nch, rot, start, W, [&](int j, int w, int n) { tcp[j] = make_int2(w, n); });
+        if (SINGLE || first) lda_row_read<L, PRE, true, true, true, true>(a.c, drows, rows, d, valid, l, V, nch, rot, start, W, [&](int j, int w, int n) { tcp[j] = make_int2(w, n); });
         // ---- Elntheta (LDA.jl:78-80), a_k = exp(Elntheta_k), theta_{t-1} (LDA.jl:92-94) ------------------------------
         double el = 0.0;
         if (ext) { if (l < KP) myA[l] = gk; }
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
             if (l < KP) myT[l] = (l < K) ? gp / Sp : 0.0;
         }
         if (first) {
-            if (stop) return;            // a previous pass met the stopping rule: this launch must not touch the state
+            if (lda_stop_now(stop)) return;            // a previous pass met the stopping rule: this launch must not touch the state
             if (SINGLE) {
 #pragma unroll
                 for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
         if (more) {
             const int nch1 = rows ? NCHR : (W1 + L - 1) / L;
             const int rot1 = nch1 > 0 ? g % nch1 : 0;
-            lda_row_read<L, PRE, true, true, true>(a.c, drows, rows, d1, valid1, l, V, nch1, rot1, start1, W1, [&](int j, int w, int n) { tcn[j] = make_int2(w, n); });
+            lda_row_read<L, PRE, true, true, true, true>(a.c, drows, rows, d1, valid1, l, V, nch1, rot1, start1, W1, [&](int j, int w, int n) { tcn[j] = make_int2(w, n); });
             gkn = (valid1 && l < K) ? io.gam[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
             gpn = (LL && valid1 && l < K) ? io.gprev[(size_t)d1 * K + l] : (l < K ? 1.0 : 0.0);
             d2 = base + 2 * stride + g; valid2 = (base + 2 * stride < D) && d2 < D;
@@ -310,14 +313,21 @@ __device__ __forceinline__ double lda_chunk_r(const int v, const double n, const
     return r;
 }
 
-template <int KP, int VT, bool RB = false>
+// R16: the corpus is rows of 16-bit counts (the default form of a single fit).  A build of its own, so that the other forms' branches -- never
+// taken over such a corpus -- do not share registers with its loads: the compiler priced the reuse of the row's address registers by the CSR
+// branch's doc_ptr load as vmcnt(0) at the join, and the row was requested only after the table and a had arrived.
+template <int KP, int VT, bool RB = false, bool R16 = false>
 __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(EstepArgs a)
 {
     static_assert(KP <= 12 && KP % 2 == 0, "topic pairs, table of <= 5 registers per thread");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int L = 16, G = MMM_WAVE / L, PRE = 96 / L;
     MMM_STAMP(0);
-    const int stop = EstepPass<RB>::stop(a);          // consumed after the prologue (its latency is hidden)
+    // one round of scalar loads for every kernel argument the block uses (left alone the compiler fetches some of them where they are first used,
+    // each a round of its own in front of the loads that follow it)
+    asm volatile("" :: "s"(a.ctl), "s"(a.aexp), "s"(a.now.gam), "s"(a.now.gnext), "s"(a.now.Eln), "s"(a.now.eB), "s"(a.c.dense16), "s"(a.c.dense), "s"(a.c.ell),
+                 "s"(a.c.doc_ptr), "s"(a.c.tc), "s"(a.c.Vp), "s"(a.c.D), "s"(a.c.K), "s"(a.c.V), "s"(a.c.alpha), "s"(a.partial), "s"(a.pstride), "s"((int)blockDim.x));
+    const int stop = EstepPass<RB>::stop_request(a);  // consumed after the prologue; a vector load ahead of every other (lda_stop_request)
     const EstepPass<RB> io(a);
     const int K = a.c.K, D = a.c.D;
     const int V = VT ? VT : a.c.V;                    // VT != 0: row stride known at compile time (immediate LDS offsets)
@@ -332,26 +342,39 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     double* myR = sR + (size_t)(wid * G + g) * Vs;
     double* myA = sA + (size_t)(wid * G + g) * KP;
 
-    // ---- document loads are issued before the table is staged (latency overlap), as in k_lda_estep --------------------------------
+    // ---- every start-up load leaves here, in one group behind the stop flag's: a (or gamma), the table, the document's row.  Unconditional,
+    //      at clamped indices (document 0 for a lane past D, topic K - 1, entry K V - 1); the masks are applied where the values are used.  One
+    //      trip to memory before the first barrier (k_lda_estep_dense: "what the dense-row kernels were actually waiting for", EXPERIMENTS.md)
     const int d = (blockIdx.x * NW + wid) * G + g;
     const bool valid = d < D;
+    const int dl = valid ? d : 0;
     const bool ext = !RB && a.aexp != nullptr;      // the previous pass's merged launch has formed a = exp(Elntheta) (EstepArgs::aexp)
-    const double gk = ext ? ((valid && l < K) ? a.aexp[(size_t)d * K + l] : 0.0) : ((valid && l < K) ? io.gam[(size_t)d * K + l] : (l < K ? 1.0 : 0.0));
-    const bool drows = a.c.dense != nullptr || a.c.dense16 != nullptr;      // rows of counts: term = slot
+    const double* __restrict__ gsrc = ext ? a.aexp : io.gam;
+    const double graw = gsrc[(size_t)dl * K + (l < K ? l : K - 1)];
+    const bool drows = R16 || a.c.dense != nullptr || a.c.dense16 != nullptr;      // rows of counts: term = slot
     const bool rows = drows || a.c.ell != nullptr;
-    const int64_t start = (valid && !rows) ? a.c.doc_ptr[d] : 0;
-    const int W = (valid && !rows) ? (int)(a.c.doc_ptr[d + 1] - start) : 0;
     constexpr int TB = KP <= 10 ? 4 : 5;            // the table stays in registers until just before the barrier (KP V <= 12 * 96, >= 4 waves; fewer waves: the loop below)
     double tb[TB];
 #pragma unroll
-    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = (i < K * V) ? io.eB[i] : 0.0; }
+    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; tb[q] = io.eB[i < K * V ? i : K * V - 1]; }
+    // (CSR's doc_ptr step after the table's loads: its lane-conditional loads end in a wait of their own, which the table's would stand behind)
+    int64_t start = 0; int W = 0;
+    if constexpr (!R16) {
+        start = (valid && !rows) ? a.c.doc_ptr[d] : 0;
+        W = (valid && !rows) ? (int)(a.c.doc_ptr[d + 1] - start) : 0;
+    }
+    unsigned w16[4] = {0u, 0u, 0u, 0u};
+    if constexpr (R16) lda_row16_load(a.c, dl, l, w16);
     // (term,count) rows and CSR visit the listed terms only: every other r is the zero written here, before the barrier the stores come after
     if (!drows) for (int i = tid; i < ND * Vs; i += blockDim.x) sR[i] = 0.0;
     MMM_STAMP(1);
 
     int tv[PRE]; double tn[PRE];      // term slot (-1: none) and count of the lane's chunks
     const int nch = rows ? NCHR : (W + L - 1) / L;
-    lda_row_read<L, PRE, false, true, true>(a.c, drows, rows, d, valid, l, V, nch, 0, start, W, [&](int j, int w, int n) { tv[j] = w; tn[j] = (double)n; });
+    auto put = [&](int j, int w, int n) { tv[j] = w; tn[j] = (double)n; };
+    if constexpr (R16) lda_row16_put<L, PRE, false, true>(w16, valid, l, V, nch, 0, put);
+    else lda_row_read<L, PRE, false, true, true, true>(a.c, drows, rows, d, valid, l, V, nch, 0, start, W, put);
+    const double gk = (valid && l < K) ? graw : ((ext || l >= K) ? 0.0 : 1.0);
     // ---- Elntheta (LDA.jl:78-80), a_k = exp(Elntheta_k) ------------------------------------------------------------------------------
     double el = 0.0, al = gk;        // al: the lane's own a_l
     if (!ext) {
@@ -359,9 +382,9 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
         al = (l < K) ? ar_exp(el) : 0.0;
     }
     if (l < KP) myA[l] = al;
-    if (stop) return;            // a previous pass met the stopping rule: this launch must not touch the state
+    if (lda_stop_now(stop)) return;            // a previous pass met the stopping rule: this launch must not touch the state
 #pragma unroll
-    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = tb[q]; }
+    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = (i < K * V) ? tb[q] : 0.0; }
     for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? io.eB[i] : 0.0;      // (waves_per_block pinned below 4)
     __syncthreads();
     MMM_STAMP(2);

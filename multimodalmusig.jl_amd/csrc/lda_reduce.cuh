@@ -75,9 +75,15 @@ __device__ __forceinline__ void lda_tail_block(const ReduceArgs& r, int lane)
 // log-likelihood numerator of pass t-1 (LDA.jl:174-188 with theta_{t-1} = gamma_{t-1} / sum, beta_{t-1}) for the documents of
 // "ll block" lb of nlb, by a block of 16 waves laid out like k_lda_reduce's (16 x 64 threads): L lanes per document (as in the
 // E-step), 64/L documents per wave step, beta staged in LDS -- the ll half of the E-step's chunk loop, moved out of it.
-template <int KP, int L>
-__device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, const double* __restrict__ bprev, double* llpart2, int lb, int nlb,
-                             double* smem, unsigned long long* cell = nullptr, unsigned int seq = 0)
+// stop: the caller's lda_stop_request (0: it has tested the flag itself).  Tested after the tables are staged, i.e. after every start-up load of the
+// block has been issued and ahead of its store to global memory: a stopped handle's block has touched registers and LDS only.  Returns true when
+// the flag was set -- the caller then leaves too, ahead of whatever it stores after the sweep (the merged launch's early prologue).
+// EARLY (the merged launch): the log table's entry is requested ahead of beta's, and both land behind ONE wait -- behind beta's it was a trip to
+// memory of its own (load, wait, store, load, wait, store).  k_lda_reduce_ll keeps the order it had: the three registers (entry, flag) are
+// 94 -> 97 VGPRs at KP = 4, a wave per SIMD less.
+template <int KP, int L, bool EARLY = false>
+__device__ bool lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, const double* __restrict__ bprev, double* llpart2, int lb, int nlb,
+                             double* smem, unsigned long long* cell = nullptr, unsigned int seq = 0, const int stop = 0)
 {
     __shared__ double s_w[16];
     const int tid = threadIdx.y * 16 + threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -114,15 +120,26 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
         const unsigned* row = at_byte((const unsigned*)c.dense16, (dl * 16u + (unsigned)l) * (unsigned)(c.Vp >> 4) * 2u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) wq[j] = row[j];
-    } else if (ell) lda_row_read<L, PRE, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
+    } else if (ell) lda_row_read<L, PRE, false, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
     int64_t start = (!ell && valid) ? c.doc_ptr[d] : 0;
     int W = (!ell && valid) ? (int)(c.doc_ptr[d + 1] - start) : 0;
     // term-major copy [v][KP] of beta_{t-1}: a lane reads the KP entries of its term as 16-byte pairs at immediate offsets (lane stride
     // 8 KP bytes: the 16 lanes of a document group cover the banks once), instead of KP reads with an address computed for each
-    for (int i = tid; i < KP * V; i += 1024) { const int v = i / KP, k = i - v * KP; sBeta[i] = (k < K) ? bprev[(size_t)k * V + v] : 0.0; }
-    if (tid < MMM_LOGTAB_N) sLog[tid] = g_mmm_logtab[tid];
+    if constexpr (EARLY) {
+        const double lt = g_mmm_logtab[tid & (MMM_LOGTAB_N - 1)];
+        for (int i = tid; i < KP * V; i += 1024) {
+            const int v = i / KP, k = i - v * KP;
+            const double b = bprev[(size_t)(k < K ? k : K - 1) * V + v];
+            sBeta[i] = (k < K) ? b : 0.0;
+        }
+        if (tid < MMM_LOGTAB_N) sLog[tid] = lt;
+    } else {
+        for (int i = tid; i < KP * V; i += 1024) { const int v = i / KP, k = i - v * KP; sBeta[i] = (k < K) ? bprev[(size_t)k * V + v] : 0.0; }
+        if (tid < MMM_LOGTAB_N) sLog[tid] = g_mmm_logtab[tid];
+    }
     MMM_RSTAMP(lb == 0 && tid == 0, 20);       // own loads (gamma row, document row, table entries) have arrived
     __syncthreads();
+    if constexpr (EARLY) { if (lda_stop_now(stop)) return true; }          // a previous pass met the stopping rule: this launch must not touch the state
     MMM_RSTAMP(lb == 0 && tid == 0, 21);       // tables staged by all waves
     double acc = 0.0;
     if (fast) {
@@ -173,7 +190,7 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
             if (base != wslot * G) {
                 d = base + g; valid = d < D;
                 gp = (valid && l < K) ? gprev[(size_t)d * K + l] : (l < K ? 1.0 : 0.0);
-                lda_row_read<L, PRE, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
+                lda_row_read<L, PRE, false, false, false, false>(c, dense, ell, d, valid, l, V, 0, 0, 0, 0, [&](int j, int w, int n) { pre[j] = make_int2(w, n); });
             }
             const double Sp = group_sum<L>(gp);
             lds_wave_sync();
@@ -228,18 +245,19 @@ __device__ void lda_ll_block(const LdaDev& c, const double* __restrict__ gprev, 
         for (int w = 0; w < 16; ++w) v += s_w[w];
         if (cell) cell_store(cell, v, seq); else llpart2[lb] = v;
     }
+    return false;
 }
 
 // grid = ceil(V*K/16) blocks of (16 entries, 64 slab lanes): fixed-order (deterministic) sum of the per-block partials
 __device__ void lda_reduce_block(const ReduceArgs& r)
 {
     __shared__ double sm[64][17];
-    const int stop = r.ctl->stop;        // only the stores depend on it: the partial loads below are issued alongside this load
+    const int stop_req = lda_stop_request(r.ctl);        // only the stores depend on it: the partial loads below are issued alongside this load
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int e = blockIdx.x * 16 + tx;
     double acc = 0.0;
     if (e < r.VK) for (int sl = ty; sl < r.nslab; sl += 64) acc += r.partial[(size_t)sl * r.VK + e];
-    if (stop) {      // a no-op pass still keeps the mailbox rendezvous of its sequence number (p2p.hip header): element 0, value unused
+    if (lda_stop_now(stop_req)) {      // a no-op pass still keeps the mailbox rendezvous of its sequence number (p2p.hip header): element 0, value unused
         if (r.p2p && blockIdx.x == 0 && tx == 0 && ty == 0) p2p_send(r.px, r.p2p_seq, 0, 0.0);
         return;
     }
@@ -348,35 +366,38 @@ __global__ __launch_bounds__(1024) void k_lda_reduce_ll_mstep(ReduceArgs r, LdaD
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ double sm2[2][64][17];
-    const int stop = r.ctl->stop;
+    // one round of scalar loads for the kernel arguments of either role's start-up (the ll blocks fetched theirs in five rounds, use by use)
+    asm volatile("" :: "s"(r.ctl), "s"(r.partial), "s"(r.nslab), "s"(r.VK), "s"(c.D), "s"(c.V), "s"(c.K), "s"(c.Vp), "s"(c.doc_ptr), "s"(c.tc), "s"(c.ell),
+                 "s"(c.dense), "s"(c.dense16), "s"(gprev), "s"(bprev), "s"(ms.nredp), "s"(ms.nred), "s"(ms.n_ll), "s"(ms.ll_join), "s"(ms.epb), "s"(ms.pro),
+                 "s"(ms.pro_gamma), "s"(ms.cells), "s"(ms.seq));
+    const int stop_req = lda_stop_request(r.ctl);      // ahead of every other load of the block, consumed ahead of its first store
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 16 + tx;
     MMM_RSTAMP(blockIdx.x == 1 && tid == 0, 0);                         // reduce block 1, wave 0
     MMM_RSTAMP(blockIdx.x == 0 && tid == 64, 8);                        // tail wave
     MMM_RSTAMP((int)blockIdx.x == ms.nredp && tid == 0, 16);             // first ll block
-    if ((int)blockIdx.x >= ms.nredp) {       // ---- ll block: numerator of pass t-1 into its cell
-        if (stop) return;
+    if ((int)blockIdx.x >= ms.nredp) {       // ---- ll block: numerator of pass t-1 into its cell (a stopped pass leaves below, ahead of the numerator's and the prologue's stores)
         constexpr int L = KP <= 15 ? 16 : (KP <= 31 ? 32 : 64);
         const int lb = (int)blockIdx.x - ms.nredp, n_ll = ms.n_ll;
         MMM_LLSTAMP(0, lb);
         // ms.pro: the block also runs the NEXT pass's prologue for its documents (the four of each wave, 16 lanes per document as
         // k_lda_estep<., 16, ...> has them): gamma_{t+1} is requested before the sweep and used after the block's numerator has left --
         // the pass tail (wave 1 of block 0, the end of this launch's critical path) does not wait a cycle longer for it
-        double gnx = 0.0;
+        double gnx = 0.0;      // (as loaded, from a clamped index: masked where it is used, after the sweep)
         int pd = 0;
         if constexpr (KP <= 12) {
             if (ms.pro) {
                 const int lane = tid & 63, l = lane & 15;
                 pd = ((tid >> 6) * n_ll + lb) * 4 + (lane >> 4);          // lda_ll_block's wave slots
-                gnx = (pd < c.D && l < c.K) ? ms.pro_gamma[(size_t)pd * c.K + l] : (l < c.K ? 1.0 : 0.0);
+                gnx = ms.pro_gamma[(size_t)(pd < c.D ? pd : 0) * c.K + (l < c.K ? l : c.K - 1)];
             }
         }
-        lda_ll_block<KP, L>(c, gprev, bprev, nullptr, lb, n_ll + (ms.ll_join ? ms.nredp - 1 : 0), smem, ms.cells + 2 * (ms.nred + lb), ms.seq);
+        if (lda_ll_block<KP, L, true>(c, gprev, bprev, nullptr, lb, n_ll + (ms.ll_join ? ms.nredp - 1 : 0), smem, ms.cells + 2 * (ms.nred + lb), ms.seq, stop_req)) return;
         MMM_RSTAMP((int)blockIdx.x == ms.nredp && tid == 0, 17);
         MMM_LLSTAMP(1, lb);
         if constexpr (KP <= 12) {
             if (ms.pro) {          // Elntheta_{t+1}, exp(Elntheta_{t+1}) (LDA.jl:78-80): the operations of the E-step kernel's prologue
                 const int lane = tid & 63, g = lane >> 4, l = lane & 15, K = c.K;
-                const double el = lda_elntheta<16>(gnx, g, l, K);
+                const double el = lda_elntheta<16>((pd < c.D && l < K) ? gnx : (l < K ? 1.0 : 0.0), g, l, K);
                 if (pd < c.D && l < K) { ms.pro_Eln[(size_t)pd * K + l] = el; ms.pro_a[(size_t)pd * K + l] = ar_exp(el); }
             }
         }
@@ -399,7 +420,7 @@ __global__ __launch_bounds__(1024) void k_lda_reduce_ll_mstep(ReduceArgs r, LdaD
             for (int sl = ty; sl < r.nslab; sl += 64) acc += r.partial[(size_t)sl * r.VK + e0];
         }
     }
-    if (stop) {      // a no-op pass still keeps the mailbox rendezvous of its sequence number (p2p.hip header): element 0, value unused
+    if (lda_stop_now(stop_req)) {      // a no-op pass still keeps the mailbox rendezvous of its sequence number (p2p.hip header): element 0, value unused
         if (P2P && rbp == 0 && tid == 0) { p2p_send(r.px, r.p2p_seq, 0, 0.0); (void)p2p_recv_sum(r.px, r.p2p_seq, 0, 0.0); }
         return;
     }

@@ -324,14 +324,23 @@ __device__ void block_inverse_wide(int n, double* A, double* Ainv, double* logde
     if (tid == 0) { double s = 0.0; for (int c = 0; c < n; ++c) s += s_col[c]; *logdet = s; }
 }
 
-// Round 5, n <= 32: the same elimination with ONE block barrier per column instead of three (35-45 us -> see DESIGN section 4.2 at n = 28).
+// Round 5, n <= 32: the same elimination with ONE block barrier per column instead of three (35-45 us -> see DESIGN section 4.6 at n = 28).
 // The matrix is the augmented [A | A^-1] of n rows x W = 2n columns and is DOUBLE-BUFFERED: the sweep of column c reads buffer `cur` and
 // writes `nxt`, so nothing waits between reading the old rows and writing the new ones.  Every update thread forms the scaled pivot entry
 // of its own column itself (low / piv: the same division, no hand-off through LDS).  Wave 0 does not sweep: while the other waves
 // eliminate column c it forms column c + 1 AS THAT SWEEP LEAVES IT (same operands, same operations: the same bits) and finds its pivot
 // (largest magnitude by DPP, lowest row by ballot -- the rule above), leaving pivot row, pivot and A[c+1][c+1] in cells of the other parity.
 // Per element the operations are exactly those of block_inverse_wide (and of the order-matched CPU restatement, orc_twin_gauss).
-// Block of >= 128 threads; M0 holds the augmented matrix on entry; returns the buffer that holds it on exit (A^-1 in columns n .. 2n-1).
+// M0 holds the augmented matrix on entry; returns the buffer that holds it on exit (A^-1 in columns n .. 2n-1).
+// Precondition (pipelined_fits): the block's threads beyond wave 0 cover the 2n columns at least once -- rstep = (nt - 64) / (2n) >= 1 -- and
+// a thread's rows r0, r0 + rstep, ... fit its registers: ceil(n / rstep) <= kPipeMaxRows (256 threads: rstep = 3 and all 11 rows at n = 32).
+constexpr int kPipeMaxRows = 11;
+__device__ __forceinline__ bool pipelined_fits(int n, int nt)
+{
+    const int rstep = (nt - 64) / (2 * n);
+    return n <= 32 && rstep >= 1 && (n + rstep - 1) / rstep <= kPipeMaxRows;
+}
+
 __device__ const double* block_inverse_pipelined(int n, double* M0, double* M1, double* logdet, int* singular)
 {
     __shared__ double s_best[64], s_lg[64], s_pv[2][2];
@@ -374,7 +383,7 @@ __device__ const double* block_inverse_pipelined(int n, double* M0, double* M1, 
                 if (r == 0) { s_best[j] = best; if (best == 0.0) *singular = 1; }
             }
         } else if (r0 < rstep) {
-            constexpr int MAXR = 11;                                // rows per thread: ceil(32 / 3)
+            constexpr int MAXR = kPipeMaxRows;                      // rows per thread: ceil(32 / 3)
             double xr[MAXR], fr[MAXR];
             int rr[MAXR];
             const double low = cur[p * W + j0], top = cur[c * W + j0];
@@ -404,7 +413,7 @@ __device__ const double* block_inverse_pipelined(int n, double* M0, double* M1, 
     return cur;
 }
 
-// update_μ! / update_Σ! of one replica by the calling block (>= 128 threads); smem: 4 MK^2 doubles (sum K <= 32: block_inverse_pipelined) or 2 MK^2.  BIG (sum K > 64): the matrices live
+// update_μ! / update_Σ! of one replica by the calling block (>= 128 threads; block_inverse_wide where pipelined_fits says no); smem: 4 MK^2 doubles (sum K <= 32: block_inverse_pipelined) or 2 MK^2.  BIG (sum K > 64): the matrices live
 // in device memory -- a compile-time switch, so that the LDS build keeps LDS addressing (a run-time choice of the base pointer turned every
 // access of the inversion into a flat one: 54 -> 84 us for the Gaussian block at sum K = 28)
 template <bool BIG>
@@ -424,7 +433,7 @@ __device__ void ctm_gauss_mstep(const MstepArgs& a, const MstepPtrs& q, double* 
     MMM_GSTAMP(1);
     // update_Σ! (MMCTM.jl:204-212) from raw moments: (diag Σν + Σ (λ-μ)(λ-μ)') / D with the NEW μ
     if (a.do_sigma) {
-        const bool pipe = !BIG && MK <= 32 && nt >= 128 && !a.gauss_wide;      // the one-barrier-per-column inversion over the augmented, double-buffered matrix
+        const bool pipe = !BIG && pipelined_fits(MK, nt) && !a.gauss_wide;      // the one-barrier-per-column inversion over the augmented, double-buffered matrix
         double* A = BIG ? a.big_scratch + (size_t)blockIdx.y * 2 * MK * MK : smem;
         double* Ai = A + MK * MK;
         const int ld = pipe ? 2 * MK : MK;                    // row stride of A in its buffer

@@ -351,7 +351,11 @@ int mmm_ctm_geometry(const mmm_ctm* m, int out[8]);
 /* Parity probe: out[i] = op(a[i], b[i]) evaluated by the device functions the kernels use (csrc/mmm_arith.h, dev_math.h).
  * op 0 exp, 1 log, 2 digamma (x > 0), 3 a / b, 4 sqrt, 5 / 6 / 7 sum over consecutive groups of 16 / 32 / 64 values in the
  * lane-butterfly order of the document groups (out[i] = total of i's group; n a multiple of 64), 8 the full-wave butterfly,
- * 9 / 10 the table-driven exp / log of the LD_MMA objectives (ar_exp_tab, ar_log_tab). */
+ * 9 / 10 the table-driven exp / log of the LD_MMA objectives (ar_exp_tab, ar_log_tab).  The device-only functions of dev_math.h:
+ * 11 dev_digamma (any x), 12 dev_rcp, 13 dev_sqrt_pos, 14 dev_log_pos, 15 dev_log_tab (the log of the log-likelihood sweeps),
+ * 16 ar_digamma_pos_tab, 17 dev_xlogx; and its collectives over each 64 consecutive values (n a multiple of 64): 18 wave_max,
+ * 19 wave_max_dpp, 20 rows_sum4 (out[i] = (a[j] + a[j + 32]) + (a[j + 16] + a[j + 48]), j = i % 16, within i's 64), 21 wave_bcast
+ * (out[i] = a[64 (i / 64) + (int)b[i]]), 22 the sum of the 64 values in index order through wave_readlane. */
 int mmm_debug_math(mmm_ctx* ctx, int op, size_t n, const double* a, const double* b, double* out);
 /* Fused hot path: n_iter passes of the body of fit! (MMCTM.jl:462-479 / IMMCTM.jl:440-451) */
 /* fit_flags: keyword arguments of fit! (MMCTM.jl:457-458): MMM_FIT_UPDATE_SIGMA = updateΣ (IMMCTM always updates Σ,

@@ -1512,6 +1512,21 @@ __global__ void k_debug_math(int op, size_t n, const double* a, const double* b,
     case 6: r = group_sum<32>(x); break;
     case 7: r = group_sum<64>(x); break;
     case 8: r = wave_sum(x); break;
+    case 11: r = dev_digamma(x); break;
+    case 12: r = dev_rcp(x); break;
+    case 13: r = dev_sqrt_pos(x); break;
+    case 14: r = dev_log_pos(x); break;
+    case 15: r = dev_log_tab(x, sTabs + MMM_EXPTAB_N); break;
+    case 16: r = ar_digamma_pos_tab(x, sTabs + MMM_EXPTAB_N); break;
+    case 17: r = dev_xlogx(x); break;
+    case 18: r = wave_max(x); break;
+    case 19: r = wave_max_dpp(x); break;
+    case 20: r = rows_sum4(x); break;
+    case 21: r = wave_bcast(x, (int)y); break;
+    case 22:
+#pragma unroll
+        for (int j = 0; j < 64; ++j) r += wave_readlane(x, j);         // index-order sum of the wave, as k_align_normalise (match.hip)
+        break;
     }
     if (i < n) out[i] = r;
 }
@@ -1520,8 +1535,8 @@ __global__ void k_debug_math(int op, size_t n, const double* a, const double* b,
 int mmm_debug_math(mmm_ctx* ctx, int op, size_t n, const double* a, const double* b, double* out)
 {
     if (!ctx) return MMM_ERR_ARG;
-    MMM_CHECK(ctx, a && out && op >= 0 && op <= 10, "mmm_debug_math: bad arguments");
-    MMM_CHECK(ctx, op < 5 || op > 8 || n % 64 == 0, "mmm_debug_math: the collectives need n %% 64 == 0");
+    MMM_CHECK(ctx, a && out && op >= 0 && op <= 22, "mmm_debug_math: bad arguments");
+    MMM_CHECK(ctx, !((op >= 5 && op <= 8) || op >= 18) || n % 64 == 0, "mmm_debug_math: the collectives need n %% 64 == 0");
     if (!n) return MMM_OK;
     MMM_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<double> da, db, dout;

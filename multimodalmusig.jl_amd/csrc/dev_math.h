@@ -43,6 +43,8 @@ __device__ __forceinline__ double dev_digamma(double x)
 
 // 1/x to <= 1 ulp: hardware reciprocal seed (v_rcp_f64) + two Newton steps.  ~6 instructions instead of the ~15 of
 // the IEEE division sequence; used where a quotient feeds a sum that is compared at >= 1e-11 relative.
+// Operand range: finite x with x and 1/x both normal (checked for 2^-1000 <= |x| <= 2^1000).  No range handling: x = +-0 and
+// x = +-inf give NaN (0 * inf in the first Newton step) where IEEE gives +-inf and +-0.
 __device__ __forceinline__ double dev_rcp(double x)
 {
     double r = __builtin_amdgcn_rcp(x);
@@ -58,6 +60,9 @@ __device__ __forceinline__ double dev_min_raw(double a, double b) { double r; as
 // a / b, bit-identical to the compiler's IEEE division whenever no operand or intermediate leaves the normal range: the
 // same rcp + 2 Newton + residual-correction sequence, without the v_div_scale / v_div_fmas / v_div_fixup range handling
 // (8 instead of ~25 instructions).  For the MMA step algebra: all operands there are O(1e-7 .. 1e7).
+// Operand range: finite a and b with 1 / b, a / b and the residual a - b q (about 2^-53 |a|) all normal, or a = 0; a, b and a / b
+// with magnitudes in [2^-900, 2^900] are sufficient and checked bit for bit.  Outside it there is no fixup: dev_div(a, +-inf) and
+// dev_div(a, 0) are NaN where IEEE gives 0 and inf, and a quotient near the ends of the exponent range is not correctly rounded.
 __device__ __forceinline__ double dev_div(double a, double b)
 {
     double y = __builtin_amdgcn_rcp(b);
@@ -67,7 +72,9 @@ __device__ __forceinline__ double dev_div(double a, double b)
     return fma(fma(-b, q, a), y, q);
 }
 
-// sqrt(x) for x = 0 or x in the normal range, the compiler's rsq-based sequence without its subnormal scaling
+// sqrt(x) for x = 0 or x in the normal range, the compiler's rsq-based sequence without its subnormal scaling.  Operand range, also
+// of dev_sqrt_pos below: finite x in [2^-900, 2^900] (checked bit for bit there; the residual x - g^2, about 2^-53 x, must stay
+// normal).  x = +inf gives NaN (inf * rsq(inf) = inf * 0) where IEEE gives +inf, and dev_sqrt_pos(0) is NaN as well.
 __device__ __forceinline__ double dev_sqrt(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -80,6 +87,7 @@ __device__ __forceinline__ double dev_sqrt(double x)
 }
 
 // the same for a NORMAL x > 0 (no zero to special-case: three instructions fewer).  For the root of the LD_MMA step, rho (|g| sigma + rho / 4) >= rho^2 / 4 > 0.
+// Operand range as dev_sqrt's, without the zero: 0 and +inf give NaN.
 __device__ __forceinline__ double dev_sqrt_pos(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -95,15 +103,19 @@ __device__ __forceinline__ double dev_sqrt_pos(double x)
 __device__ __forceinline__ double dev_digamma_pos(double x) { return ar_digamma_pos(x); }
 __device__ __forceinline__ double dev_digamma_ar(double x) { return (x > 0.0 && x < 1e40) ? ar_digamma_pos(x) : dev_digamma(x); }
 
-// natural log of a NORMAL x > 0 from a 128-interval table in LDS (csrc/mmm_logtab.h, staged by the caller: tab[2 j] = 1 / c_j,
+// natural log from a 128-interval table in LDS (csrc/mmm_logtab.h, staged by the caller: tab[2 j] = 1 / c_j,
 // tab[2 j + 1] = log c_j, c_j the midpoint of the mantissa interval): x = 2^e m, r = m / c_j - 1 (|r| < 2^-8), log x = e ln 2 + log c_j
-// + log1p(r) with log1p by its series to r^6.  15 instructions and one 16-byte LDS read instead of ~35; absolute error < 5e-16
-// (2.5e-15 relative where |log x| > 0.05) -- for the log-likelihood sweeps, whose sums are compared at 1e-9.
+// + log1p(r) with log1p by its series to r^6.  15 instructions and one 16-byte LDS read instead of ~35.  For a normal x > 0 it is
+// ar_log_tab (mmm_arith.h) bit for bit: absolute error < 2.5e-15 for x <= 30 (a few ulp of |log x| away from 1), as tested for that
+// function -- for the log-likelihood sweeps, whose sums are compared at 1e-9.  Unlike ar_log_tab it is defined for every x, because a
+// sweep must hand on whatever its probabilities are: +-0 -> -inf, subnormals through dev_log_pos, x < 0 and NaN of either sign -> NaN,
+// +inf -> +inf (one unsigned range test on the high word sends all of them down the unlikely branch).
 __device__ __forceinline__ double dev_log_pos(double x);
 __device__ __forceinline__ double dev_log_tab(double x, const double* __restrict__ tab)
 {
     const int hi = __double2hiint(x), lo = __double2loint(x);
-    if (__builtin_expect(hi < 0x00100000, 0)) return x > 0.0 ? dev_log_pos(x) : (x == 0.0 ? -__builtin_inf() : __builtin_nan(""));      // zero, subnormal, negative: as log()
+    if (__builtin_expect((unsigned)(hi - 0x00100000) >= 0x7fe00000u, 0))       // anything but a normal x > 0: as log().  (dev_log_pos(+inf) is inf * rcp(inf) = NaN)
+        return x > 0.0 ? (hi >= 0x7ff00000 ? x : dev_log_pos(x)) : (x == 0.0 ? -__builtin_inf() : __builtin_nan(""));
     const int e = (hi >> 20) - 1023, j = (hi >> 13) & 127;
     const double m = __hiloint2double((hi & 0x000fffff) | 0x3ff00000, lo);
     const double2 t = *reinterpret_cast<const double2*>(tab + 2 * j);
@@ -142,8 +154,8 @@ __device__ __forceinline__ double dev_log_pos(double x)
     return fma(dk, 6.93147180369123816490e-01, f - (hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)));
 }
 
-// x*log(x) with the reference's 0^0 = 1 convention of log(x^x) (LDA.jl:157; MMCTM.jl:365)
-__device__ __forceinline__ double dev_xlogx(double x) { return x > 0.0 ? x * log(x) : 0.0; }
+// x*log(x) with the reference's 0^0 = 1 convention of log(x^x) (LDA.jl:157; MMCTM.jl:365); NaN stays NaN and x < 0 becomes NaN, as there
+__device__ __forceinline__ double dev_xlogx(double x) { return x == 0.0 ? 0.0 : x * log(x); }
 
 // ---- cross-lane ---------------------------------------------------------------------------------------
 // full-wave (64 lanes) butterfly sum: every lane ends with the total

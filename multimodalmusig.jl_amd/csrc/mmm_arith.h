@@ -128,7 +128,10 @@ AR_FN double ar_exp_tab(double x, const double* tab)
 /* log(x) for NORMAL x > 0 (the nu of an LD_MMA solve: >= its lower bound 1e-7): x = 2^e m, m in [1, 2), interval j = top 7 mantissa
  * bits with midpoint c_j, r = m / c_j - 1 (|r| < 2^-8; the table holds 1 / c_j and log c_j), log x = e ln 2 + log c_j + log1p(r),
  * log1p by its series to r^6.  Absolute error < 2.5e-15 for x <= 30 (a few ulp of |log x| away from 1; the objective it enters is
- * O(10..1e4), i.e. it stays below that sum's own rounding); no division. */
+ * O(10..1e4), i.e. it stays below that sum's own rounding); no division.  NORMAL x > 0 ONLY: there is no special case at all, so zero,
+ * subnormals, negative numbers, +inf and NaN come out as finite numbers (+inf as 709.78, a positive NaN as 710.19).  The LD_MMA nu is
+ * bounded below by 1e-7 and finite.  The device's log-likelihood sweeps, whose probabilities may be anything, go through dev_log_tab
+ * (dev_math.h) for this reason: the same bits for a normal x > 0, log()'s results for everything else. */
 AR_FN double ar_log_tab(double x, const double* tab)
 {
     const unsigned long long u = AR_BITS(x);

@@ -1,6 +1,7 @@
 """Frozen-topic inference: transform / fit_heldout / predict_modality_η on the HIP backend against the CPU
 oracle's restatement of LDA.jl:226-295, MMCTM.jl:496-634, IMMCTM.jl:468-545, and the reference's own test of `transform`
-(test/mmctm.jl:390-406)."""
+(test/mmctm.jl:390-406).  The LDA tests here run three shapes; tests/test_lda_infer_dispatch_gpu.py walks every E-step build that
+LDA inference can take against tests/lda_infer_ref.py."""
 import warnings
 
 import numpy as np

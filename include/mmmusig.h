@@ -559,6 +559,46 @@ int mmm_refit_exposures(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_pt
                         const uint8_t* allowed, const double* penalty, int maxiter, double tol, double* w, uint8_t* active, int32_t* order, double* cost,
                         double* ll_doc, double* unexplained, int64_t* iters);
 
+/* ---- model simulation and per-sample goodness of fit by a parametric bootstrap (no counterpart in the reference).
+ * props [k + K d] and phi [k V + v] as mmm_mixture_score takes them, every entry >= 0 and finite; rows need not be normalised.
+ * Per document d:
+ * Mixture.  p_v = sum_k props[k + K d] * phi[k V + v], k ascending, product and sum rounded separately (mmm_mixture_score's p);
+ *   cum_v = the inclusive sum of p over v ascending, strictly sequential; S = cum_{V-1}; pi_v = p_v / S (an IEEE division).
+ * Thresholds.  T_v = floor((cum_v / S) * 2^32), an integer in [0, 2^32]: non-decreasing, T_{V-1} = 2^32 exactly, and a term with p_v = 0
+ *   has T_v = T_{v-1}.
+ * Draws.  Draw i < N_d of replicate b (the GLOBAL index b0 + ..., so chunked calls are slices of one big call) uses output word i % 4 of
+ *   the Philox4x32-10 block with the constants and the key of mmm_resample_counts and the counter (i / 4, d, 0x80000000 | b, stream), d
+ *   being the document's index in the arrays given.  The high bit of the third counter word is free in mmm_resample_counts and in
+ *   mmm_split_counts (both keep b, rep < 2^31), so a simulation shares no random word with either, whatever the stream.  With u that
+ *   word, the draw lands on the first v with T_v > u.  Integer throughout; a term with p_v = 0 never receives a draw; the resolution is
+ *   2^-32 per term and is not corrected, as with the resampler.  A replicate is the vector of draws per term: it sums to N_d.
+ * Statistics of a count vector n with total N over the V terms (for the observed document: the dense vector, duplicate terms summed):
+ *   cosine = (sum_v n_v pi_v) / (sqrt(sum_v n_v^2) * sqrt(sum_v pi_v^2)), 0 where a norm is 0;
+ *   chi2 = sum_v t_v, with t_v = ((n_v - e_v) * (n_v - e_v)) / e_v and e_v = N * pi_v where pi_v > 0; where pi_v = 0, t_v = +inf if
+ *   n_v > 0, else 0.
+ *   Each of the four sums is 64 partial sums, partial l over v = l, l + 64, ... ascending from 0.0, combined by the butterfly of
+ *   mmm_mixture_score's cosine sums (l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1).  Every product, sum, difference, division and square
+ *   root is a separate, correctly rounded operation; there is no log.  So every output is decided by exactly rounded operations in a
+ *   fixed order: the same arguments give the same bits on every run and under every launch geometry; a document gives the same bits
+ *   whatever its neighbours as long as its index d is the same; a call with (b0, B) is a slice of the call with (0, b0 + B).
+ * N_d = 0: nothing is drawn; the replicates are all-zero rows, both statistics and every replicate value are 0, both counts are B.
+ * MMM_ERR_ARG, nothing written: NULL pointers, K < 1, V < 1, D < 0, B < 0, b0 < 0, b0 + B > 2^31 - 1, a negative n_doc or count, a corpus
+ *   that is no CSR of terms < V, a props or phi entry that is negative or not finite, a document with N_d > 0 whose S is 0 or not finite
+ *   (the message names it).  MMM_ERR_UNSUPPORTED, with the limit in the message: N_d >= 2^31; V > 4096 (a block keeps pi, the thresholds
+ *   and its histograms in LDS).  Any K >= 1.  No collective: on a multi-rank context both act on the arrays they are given. */
+/* out[(b D + d) V + v], b < B: the draws on term v of replicate b0 + b of document d, n_doc[d] of them.  Replicates go through a bounded
+ * device buffer in chunks.  B = 0 or D = 0: MMM_OK, nothing written. */
+int mmm_simulate_counts(mmm_ctx* ctx, int D, int K, int V, const double* props, const double* phi, const int32_t* n_doc /* [D] */, int B, int b0,
+                        uint64_t seed, uint32_t stream, int32_t* out /* [B][D][V] */);
+/* CSR corpus as mmm_mixture_score takes it; N_d is the sum of the document's counts.  cos_obs, chi_obs [D]: the statistics of the observed
+ * vector.  Replicate (d, b) is exactly the vector mmm_simulate_counts gives for the same arguments with n_doc[d] = N_d; it never leaves
+ * the device.  cos_le[d] = the number of b with cos_rep <= cos_obs, chi_ge[d] = the number of b with chi_rep >= chi_obs, over the B
+ * replicates of THIS call (the counts of chunked calls add).  cos_rep, chi_rep: [b D + d] the replicates' statistics, or NULL.
+ * B = 0: the observed statistics and zero counts.  D = 0: nothing written. */
+int mmm_fit_check(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* props,
+                  const double* phi, int B, int b0, uint64_t seed, uint32_t stream, double* cos_obs, double* chi_obs /* [D] */, int32_t* cos_le,
+                  int32_t* chi_ge /* [D] */, double* cos_rep, double* chi_rep /* [B][D] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

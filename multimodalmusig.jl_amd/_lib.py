@@ -145,6 +145,8 @@ _SIGS = {
     "mmm_mixture_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, f64p, vp, vp, vp, f64p]),
     "mmm_lda_score_replicas": (C.c_int, [vp, i64p, vp, vp, f64p, vp, vp]),
     "mmm_refit_exposures": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, vp, vp, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_simulate_counts": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp]),
+    "mmm_fit_check": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
 }
 
 

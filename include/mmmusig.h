@@ -95,7 +95,7 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_CTM_PIPE_GAUSS = 1 << 12,    /* Gaussian M-step: the three-barrier-per-column inversion instead of the pipelined one (sum K <= 32); same bits         */
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
     MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
-    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures: read the catalogue through L2 even where it fits LDS; same bits                                           */
+    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
     MMM_OFF_ALL = (1 << 16) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
 typedef struct {
@@ -598,6 +598,41 @@ int mmm_simulate_counts(mmm_ctx* ctx, int D, int K, int V, const double* props, 
 int mmm_fit_check(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* props,
                   const double* phi, int B, int b0, uint64_t seed, uint32_t stream, double* cos_obs, double* chi_obs /* [D] */, int32_t* cos_le,
                   int32_t* chi_ge /* [D] */, double* cos_rep, double* chi_rep /* [B][D] or NULL */);
+
+/* ---- is signature t present in document d?  A likelihood-ratio statistic per (target, document) and its null distribution by a parametric
+ * bootstrap, in one call (no counterpart in the reference).  CSR corpus, cat and allowed as mmm_refit_exposures
+ * takes them; P, n_v, N, f_v, fit(A) with the order of its sums, ll(A) and u(A) are those of mmm_refit_exposures.
+ * Items.  Item j = t_idx D + d for t_idx in [0, T) and document d; t = targets[t_idx].  A1 = allowed_d + {t}, A0 = allowed_d - {t}
+ *   (allowed == NULL: the whole catalogue), so t is always in A1 and never in A0.
+ * Statistic of a count vector n of total N.  Null fit: (w0, ll0, u0) = fit(A0).  Score: s = sum_v r_v P[t][v] with r_v = f_v / q0_v where
+ *   n_v > 0 and q0_v > 0, else 0, q0 the mixture of the NORMALISED w0; the sum as 64 partial sums (v = l, l + 64, ... ascending) and the
+ *   butterfly of fit(A); no log enters s.
+ *   u0 = 0 and not (s > 1):  Lambda = 0 exactly and fit(A1) is NOT run -- the mixture likelihood is concave in w and s <= 1 is the
+ *     Karush-Kuhn-Tucker condition for the null optimum to be the optimum over A1.
+ *   u0 = 0 and s > 1:  (w1, ll1, u1) = fit(A1), Lambda = max(2 (ll1 - ll0), 0).
+ *   u0 > 0 (the null cannot produce some mutation):  fit(A1) runs; Lambda = +inf if u1 < u0, else max(2 (ll1 - ll0), 0).
+ * Observed.  status[j] = 3: N_d = 0 or A0 empty, untestable -- every other output of the item is 0 (the caller's p is NaN); 1: Lambda_obs = 0,
+ *   count_ge = B and no replicate is run; 2: Lambda_obs = +inf, count_ge = 0 and no replicate is run; 0: tested by the replicates below.
+ *   w_null[j][.] = w0 (exactly 0 outside A0), score[j] = s, stat[j] = Lambda_obs, w_alt[j] = w1_t (0 where fit(A1) did not run).
+ * Replicates (status 0).  Replicate b in [b0, b0 + B) of item j is the draw of mmm_simulate_counts for document j of a T D-document corpus
+ *   with the props row w_null[j][.], phi = P and the total N_d: the sequential cum, T_v = floor((cum_v / S) 2^32), the counter
+ *   (i / 4, j, 0x80000000 | b, stream) under the key (seed low, seed high) -- deliberately the words mmm_simulate_counts(w_null, P, N) uses
+ *   under the same (seed, stream), so that the replicates can be reproduced through it (and a goodness of fit under the same seed and
+ *   stream is correlated with this test).  Lambda_b is the statistic of the replicate.  count_ge[j] = #{b : Lambda_b >= Lambda_obs},
+ *   count_zero[j] = #{b : Lambda_b = 0} over the B replicates of THIS call (the counts of chunked calls add); p = (1 + count_ge) / (B + 1) is
+ *   the caller's.  rep_stat (or NULL): [b T D + j] = Lambda_b, NaN for the items without replicates.
+ * iters[j]: the EM iterations of all the item's fits, the replicates' of this call included.
+ * w_null, score, the branch taken (observed and in every replicate), the draws, status, count_zero and iters are decided by +, x, / and
+ *   comparisons in a fixed order: the same bits on every run, under every launch geometry and wherever the catalogue is read from.  Lambda and
+ *   count_ge pass through the device log (< 1 ulp per term), as ll of mmm_refit_exposures does.
+ * Limits: 1 <= C <= 256, 1 <= V <= 4096, T >= 1, T D < 2^31, N_d < 2^31, b0 + B <= 2^31 - 1; B = 0 runs the observed phase only; D = 0 writes
+ *   nothing.  MMM_ERR_ARG, nothing written: NULL pointers, a target outside [0, C), B < 0, b0 < 0, b0 + B > 2^31 - 1, maxiter < 1, tol < 0 and
+ *   the catalogue and corpus errors of mmm_refit_exposures.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256, V > 4096,
+ *   T D >= 2^31, N_d >= 2^31.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                      const uint8_t* allowed /* [D][C] or NULL */, int T, const int32_t* targets /* [T] */, int B, int b0, uint64_t seed, uint32_t stream,
+                      int maxiter, double tol, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */, int32_t* count_ge,
+                      int32_t* count_zero, int8_t* status, int64_t* iters, double* rep_stat /* [B][T D] or NULL */);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,526 @@
+// presence.hip -- mmm_presence_test: is signature t present in document d?  A likelihood-ratio statistic per (target, document) item and its
+// null distribution by a parametric bootstrap, draws, both fits and the comparison in one launch (no counterpart in the reference;
+// include/mmmusig.h has the normative definition, DESIGN.md section 4.15 the reasoning).
+//
+// Two phases on the context's stream.  "Observed": one wave per item behind a work counter, as k_refit hands out documents; it leaves the
+// null weights, the score, the statistic and the status of every item.  "Replicates": grid (status-0 item, replicate chunk); a block stages
+// the rows of the item's signatures in LDS (where they fit), forms the mixture of the null weights and its integer thresholds exactly as
+// k_simulate does, and then every wave takes one replicate at a time: Philox draws into its own LDS histogram, f = n / N, the null fit,
+// the score, the alternative fit only where the score exceeds 1, one comparison.  The replicate's counts never leave LDS.
+// Lane l owns the terms v = l, l + 64, ...; the sums of fit(A) are those of refit.hip (refit_reduce.cuh), the draw is simulate.hip's.
+#include "mmm_internal.h"
+#include "dev_math.h"
+#include "mmm_philox.h"
+#include "refit_reduce.cuh"
+
+namespace {
+
+constexpr int kPrMaxC = 256;
+constexpr int kPrMaxV = 4096;                   // k_simulate's limit: the threshold row and a wave's buffers stay in LDS
+constexpr int kPrMaxWaves = 8;                  // 8 waves of up to 256 VGPRs fill a CU: two per SIMD
+constexpr size_t kPrLdsBlock = 160 * 1024;      // LDS a block may take (the CU's)
+constexpr uint32_t kPrSimBit = 0x80000000u;     // high bit of the third counter word: the words of mmm_simulate_counts
+
+struct PrArgs {
+    int D, C, V, Cp, T, maxiter;
+    double tol;
+    const int64_t* doc_ptr; const int32_t* term; const int32_t* count;      // observed phase
+    const double* P;                 // [C][V], rows normalised
+    const uint8_t* allowed;          // [D][C] or NULL
+    const int32_t* targets;          // [T]
+    double* w_null; double* stat; double* score; double* w_alt; int8_t* status; unsigned long long* iters;     // [T D] (w_null [T D][C])
+    int* counter;                    // next item of the observed phase
+    // replicate phase
+    const int32_t* items;            // the status-0 items this launch takes
+    const int32_t* n_doc;            // [D] totals
+    int B, reps_per_block, P2, wave_doubles, stage_doubles;     // stage_doubles: the LDS of the staged rows (even), 0 in the observed phase
+    uint32_t b0, k0, k1, stream;
+    int32_t* count_ge; int32_t* count_zero;
+    double* rep;                     // [B][T D] or NULL
+};
+
+// a wave's own LDS: the weights of the null and the alternative fit, the two lists of signatures (in the order of c, padded to a multiple
+// of 64 with a valid row whose results are dropped), f_v, r_v and the count vector
+struct PrWave {
+    double* w0; double* w1; int* act1; int* act0; double* fb; double* rb; uint32_t* hist;
+};
+
+__host__ __device__ inline int pr_wave_doubles(int Cp, int V) { return (3 * Cp + 2 * V + (V + 1) / 2 + 1) & ~1; }
+
+__device__ __forceinline__ PrWave pr_carve(double* base, int Cp, int V)
+{
+    PrWave w;
+    w.w0 = base; w.w1 = base + Cp;
+    w.act1 = (int*)(base + 2 * (size_t)Cp); w.act0 = w.act1 + Cp;
+    w.fb = base + 3 * (size_t)Cp; w.rb = w.fb + V;
+    w.hist = (uint32_t*)(w.rb + V);
+    return w;
+}
+
+// A1 = allowed_d + {t} as the list act1 (catalogue rows in the order of c) and A0 = A1 - {t} as act0, both padded.  Returns |A1|; tpos: the
+// place of t in act1.
+__device__ __forceinline__ int pr_lists(const PrArgs& a, int d, int t, const PrWave& w, int lane, int& tpos)
+{
+    const int C = a.C;
+    int n1 = 0, tp = 0;
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int c = c0 + lane;
+        const bool on = c < C && (c == t || (a.allowed ? a.allowed[(size_t)d * C + c] != 0 : true));
+        const unsigned long long m = __ballot(on);
+        if (on) w.act1[n1 + __popcll(m & ((1ull << lane) - 1ull))] = c;
+        if (c0 == (t & ~63)) tp = n1 + __popcll(m & ((1ull << (t & 63)) - 1ull));
+        n1 += __popcll(m);
+    }
+    rf_wave_sync();
+    const int n0 = n1 - 1;
+    for (int i = lane; i < n0; i += 64) w.act0[i] = w.act1[i < tp ? i : i + 1];
+    rf_wave_sync();
+    for (int i = n1 + lane; i < ((n1 + 63) & ~63); i += 64) w.act1[i] = w.act1[0];
+    if (n0 > 0)
+        for (int i = n0 + lane; i < ((n0 + 63) & ~63); i += 64) w.act0[i] = w.act0[0];
+    rf_wave_sync();
+    tpos = tp;
+    return n1;
+}
+
+// The statistic of the count vector in w.hist (total N, f_v in w.fb) for the lists w.act0 (n0 >= 1 rows) and w.act1 (n0 + 1 rows, the
+// target at tpos); trow: the target's row of P.  fit(A) is k_refit's, instruction for instruction: the cold start, q_v sequentially over the
+// list, the 64 partial sums of g_c through the transposing butterfly, the normalisation, ll and u.  Pass 0 is the null fit and ends with
+// the score s = sum_v r_v P[t][v] under the normalised null weights (the lane is the partial sum, wave_sum the butterfly); pass 1, the
+// alternative fit, runs only where the definition asks for it.  Leaves the null weights in w.w0 and the alternative ones in w.w1.
+struct PrStat {
+    double lam, s;
+    bool alt;
+    int iters;
+};
+
+__device__ __forceinline__ PrStat pr_statistic(const double* __restrict__ P, const PrWave& w, int n0, int trow, int V, int lane, int maxiter, double tol)
+{
+    const uint32_t* hist = w.hist;
+    const double* fb = w.fb;
+    double* rb = w.rb;
+    double ll0 = 0.0, u0 = 0.0, ll1 = 0.0, u1 = 0.0, s = 0.0;
+    int iters = 0;
+    bool alt = false;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int* cact = pass ? w.act1 : w.act0;
+        double* cw = pass ? w.w1 : w.w0;
+        const int cn = n0 + pass;
+        const double wc = 1.0 / (double)cn;
+        for (int i = lane; i < cn; i += 64) cw[i] = wc;
+        rf_wave_sync();
+        int it = 0;
+        while (it < maxiter) {
+            ++it;
+            // two of the lane's terms at a time: their sums over c are independent chains (each still in the order of c)
+            for (int v = lane; v < V; v += 128) {
+                const bool two = v + 64 < V;
+                const int v1 = two ? v + 64 : v;
+                double q = 0.0, q1 = 0.0;
+#pragma unroll 4
+                for (int i = 0; i < cn; ++i) {
+                    const double wi = cw[i];
+                    const int row = cact[i] * V;
+                    q += wi * P[row + v];
+                    q1 += wi * P[row + v1];
+                }
+                rb[v] = (hist[v] != 0u && q > 0.0) ? fb[v] / q : 0.0;
+                if (two) rb[v1] = (hist[v1] != 0u && q1 > 0.0) ? fb[v1] / q1 : 0.0;
+            }
+            rf_wave_sync();
+            double md = 0.0;
+            for (int b = 0; b < cn; b += 32) {
+                const int m = min(32, cn - b);
+                double g; int j;
+                if (m <= 4) { g = rf_gchunk<2>(P, cact + b, rb, V, lane); j = lane >> 4; }
+                else if (m <= 8) { g = rf_gchunk<3>(P, cact + b, rb, V, lane); j = lane >> 3; }
+                else if (m <= 16) { g = rf_gchunk<4>(P, cact + b, rb, V, lane); j = lane >> 2; }
+                else { g = rf_gchunk<5>(P, cact + b, rb, V, lane); j = lane >> 1; }
+                if (j < m) {
+                    const double wo = cw[b + j], wn = wo * g;
+                    md = fmax(md, fabs(wn - wo));
+                    cw[b + j] = wn;           // the lanes that share j write the same bits
+                }
+            }
+            rf_wave_sync();
+            if (wave_max(md) < tol) break;
+        }
+        iters += it;
+        double S = 0.0;
+        for (int i = 0; i < cn; ++i) S += cw[i];
+        rf_wave_sync();
+        if (S > 0.0)
+            for (int i = lane; i < cn; i += 64) cw[i] = cw[i] / S;
+        rf_wave_sync();
+        double lp = 0.0, up = 0.0, sp = 0.0;
+        for (int v = lane; v < V; v += 64) {
+            double q = 0.0;
+            for (int i = 0; i < cn; ++i) q += cw[i] * P[cact[i] * V + v];
+            const uint32_t ni = hist[v];
+            if (ni != 0u) {
+                const double nv = (double)ni;
+                if (q > 0.0) {
+                    lp += nv * log(q);
+                    if (pass == 0) sp += (fb[v] / q) * P[trow * V + v];
+                } else up += nv;
+            }
+        }
+        if (pass == 0) {
+            ll0 = wave_sum(lp); u0 = wave_sum(up); s = wave_sum(sp);
+            if (u0 == 0.0 && !(s > 1.0)) break;        // the null optimum is the optimum over A1 (KKT): the statistic is 0 exactly
+        } else {
+            ll1 = wave_sum(lp); u1 = wave_sum(up); alt = true;
+        }
+    }
+    PrStat r;
+    r.s = s; r.alt = alt; r.iters = iters;
+    r.lam = !alt ? 0.0 : ((u0 > 0.0 && u1 < u0) ? __builtin_inf() : fmax(2.0 * (ll1 - ll0), 0.0));
+    return r;
+}
+
+// Observed phase.  Dynamic LDS: per wave pr_wave_doubles doubles; the catalogue is read through L2 (one fit or two per item: a B-th of the
+// call's work).  The host has zeroed every output; an untestable item (N = 0 or A0 empty) gets its status and nothing else.
+__global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_obs(const PrArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_pr[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int C = a.C, V = a.V;
+    const PrWave w = pr_carve(s_pr + (size_t)wave * a.wave_doubles, a.Cp, V);
+    const double* __restrict__ P = a.P;
+    const int TD = a.T * a.D;
+    for (;;) {
+        int j = 0;
+        if (lane == 0) j = atomicAdd(a.counter, 1);
+        j = __shfl(j, 0, 64);
+        if (j >= TD) break;
+        const int d = j % a.D, t = a.targets[j / a.D];
+        // ---- n_v (duplicate terms summed), N, f_v
+        for (int v = lane; v < V; v += 64) w.hist[v] = 0u;
+        rf_wave_sync();
+        double Np = 0.0;
+        for (int64_t e = a.doc_ptr[d] + lane; e < a.doc_ptr[d + 1]; e += 64) {
+            const int cnt = a.count[e];
+            if (cnt > 0) { atomicAdd(&w.hist[a.term[e]], (uint32_t)cnt); Np += (double)cnt; }
+        }
+        const double N = wave_sum(Np);             // integers below 2^31: exact in any order
+        rf_wave_sync();
+        for (int v = lane; v < V; v += 64) w.fb[v] = N > 0.0 ? (double)w.hist[v] / N : 0.0;
+        int tpos;
+        const int n0 = pr_lists(a, d, t, w, lane, tpos) - 1;
+        if (N == 0.0 || n0 == 0) {
+            if (lane == 0) a.status[j] = 3;
+        } else {
+            const PrStat r = pr_statistic(P, w, n0, t, V, lane, a.maxiter, a.tol);
+            for (int i = lane; i < n0; i += 64) a.w_null[(size_t)j * C + w.act0[i]] = w.w0[i];
+            if (lane == 0) {
+                a.stat[j] = r.lam; a.score[j] = r.s;
+                a.w_alt[j] = r.alt ? w.w1[tpos] : 0.0;
+                a.status[j] = r.lam == 0.0 ? 1 : (r.lam == __builtin_inf() ? 2 : 0);
+                a.iters[j] = (unsigned long long)r.iters;
+            }
+        }
+        // every path ends here, the whole wave together: a `continue` after the lane-0 store above lets the compiler thread lane 0 straight into
+        // the lane-0 fetch of the next item, and the other 63 lanes then take their item from a lane that is not there
+        rf_wave_sync();
+    }
+}
+
+// One wave draws the N draws of replicate b of item j into hist: simulate.hip's sim_draw_row (the same counter words, the same search over
+// the thresholds T_v - 1 of the terms v >= z, padded with 0xffffffff to the power of two P2), on an unsigned histogram.
+__device__ __forceinline__ void pr_draw(int lane, int P2, int z, uint32_t N, const uint32_t* thr, uint32_t* hist, uint32_t j, uint32_t b, uint32_t stream,
+                                        uint32_t k0, uint32_t k1)
+{
+    const uint32_t nblk = (N + 3u) >> 2;                       // N < 2^31
+    for (uint32_t i4 = (uint32_t)lane; i4 < nblk; i4 += 64u) {
+        uint32_t u[4];
+        int pos[4];
+        philox4x32_10(i4, j, kPrSimBit | b, stream, k0, k1, u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pos[k] = 0;
+        for (int step = P2 >> 1; step > 0; step >>= 1) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (thr[pos[k] + step - 1] < u[k]) pos[k] += step;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4u * i4 + (uint32_t)k < N) atomicAdd(&hist[z + pos[k]], 1u);
+    }
+}
+
+// Replicate phase: grid (items, replicate chunks), blockDim 64 nw.  Dynamic LDS: int z (16 bytes) | uint32 thr[P2] | P_LDS: the rows of A1 at
+// stride V | per wave pr_wave_doubles doubles.  The mixture p and its running sums are formed where wave 0's f and r follow.
+template <bool P_LDS>
+__global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_rep(const PrArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_pr[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (int)(blockDim.x >> 6), nt = (int)blockDim.x;
+    const int C = a.C, V = a.V, P2 = a.P2;
+    const int j = a.items[blockIdx.x], d = j % a.D, t = a.targets[j / a.D], TD = a.T * a.D;
+    int* s_z = (int*)s_pr;
+    uint32_t* s_thr = (uint32_t*)(s_pr + 2);
+    double* s_rows = s_pr + 2 + P2 / 2;                        // P2 >= 4: 16-byte steps
+    double* wave_base = s_rows + (P_LDS ? a.stage_doubles : 0);
+    // every wave builds the lists for itself (the same bits): no wave waits for another after the set-up
+    const PrWave w = pr_carve(wave_base + (size_t)wave * a.wave_doubles, a.Cp, V);
+    int tpos;
+    const int n1 = pr_lists(a, d, t, w, lane, tpos);           // <= stage_doubles / V where the rows are staged: the host sorts the items
+    const int n0 = n1 - 1;
+    // the observed null weights, in the order of the list
+    for (int i = lane; i < n0; i += 64) w.w0[i] = a.w_null[(size_t)j * C + w.act0[i]];
+    int trow = t;
+    if (P_LDS) {
+        for (int i = wave; i < n1; i += nw) {
+            const double* src = a.P + (size_t)w.act1[i] * V;
+            for (int v = lane; v < V; v += 64) s_rows[(size_t)i * V + v] = src[v];
+        }
+        rf_wave_sync();
+        for (int i = lane; i < ((n1 + 63) & ~63); i += 64) w.act1[i] = i < n1 ? i : 0;
+        for (int i = lane; i < ((n0 + 63) & ~63); i += 64) w.act0[i] = i < n0 ? (i < tpos ? i : i + 1) : (tpos == 0 ? 1 : 0);
+        trow = tpos;
+    }
+    const double* __restrict__ P = P_LDS ? s_rows : a.P;
+    if (tid == 0) *s_z = 0;
+    __syncthreads();
+    // ---- p_v = sum_c w0_c P[c][v] (the zero weights outside A0 add nothing: same bits as the sum over all C), cum, S, thresholds: k_simulate's
+    double* s_p = pr_carve(wave_base, a.Cp, V).fb;
+    double* s_cum = s_p + V;
+    for (int v = tid; v < V; v += nt) {
+        double p = 0.0;
+        for (int i = 0; i < n0; ++i) p += w.w0[i] * P[w.act0[i] * V + v];
+        s_p[v] = p;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double c = 0.0;
+        for (int v = 0; v < V; ++v) { c += s_p[v]; s_cum[v] = c; }
+    }
+    __syncthreads();
+    const double S = s_cum[V - 1];
+    if (!(S > 0.0 && S <= 1.7976931348623157e308)) return;     // no status-0 item has such a null fit; without thresholds nothing may be drawn
+    const double two32 = 4294967296.0;
+    int nz = 0;
+    for (int v = tid; v < V; v += nt) nz += (unsigned long long)((s_cum[v] / S) * two32) == 0ull;
+    if (nz) atomicAdd(s_z, nz);
+    __syncthreads();
+    const int z = *s_z;                                        // T is non-decreasing and T_{V-1} = 2^32: the zeros lead, z <= V - 1
+    for (int v = tid; v < V; v += nt) {
+        const unsigned long long T = (unsigned long long)((s_cum[v] / S) * two32);       // floor: the product is exact and >= 0
+        if (v >= z) s_thr[v - z] = (uint32_t)(T - 1ull);
+    }
+    for (int k = V - z + tid; k < P2; k += nt) s_thr[k] = 0xffffffffu;
+    __syncthreads();                                           // the running sums are read; wave 0's f and r take their place
+    // ---- the wave's replicates
+    const uint32_t N = (uint32_t)a.n_doc[d];
+    const double Nd = (double)N, lam_obs = a.stat[j];
+    const int bbeg = (int)blockIdx.y * a.reps_per_block, bend = min(a.B, bbeg + a.reps_per_block);
+    for (int v = lane; v < V; v += 64) w.hist[v] = 0u;
+    rf_wave_sync();
+    int ge = 0, zero = 0;
+    unsigned long long its = 0ull;
+    for (int b = bbeg + wave; b < bend; b += nw) {
+        pr_draw(lane, P2, z, N, s_thr, w.hist, (uint32_t)j, a.b0 + (uint32_t)b, a.stream, a.k0, a.k1);
+        rf_wave_sync();
+        for (int v = lane; v < V; v += 64) w.fb[v] = (double)w.hist[v] / Nd;
+        rf_wave_sync();
+        const PrStat r = pr_statistic(P, w, n0, trow, V, lane, a.maxiter, a.tol);
+        ge += r.lam >= lam_obs; zero += r.lam == 0.0; its += (unsigned long long)r.iters;
+        if (a.rep && lane == 0) a.rep[(size_t)b * TD + j] = r.lam;
+        for (int v = lane; v < V; v += 64) w.hist[v] = 0u;
+        rf_wave_sync();
+    }
+    if (lane == 0) {
+        if (ge) atomicAdd(&a.count_ge[j], ge);
+        if (zero) atomicAdd(&a.count_zero[j], zero);
+        if (its) atomicAdd(&a.iters[j], its);
+    }
+}
+
+} // namespace
+
+extern "C" int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                                 const uint8_t* allowed, int T, const int32_t* targets, int B, int b0, uint64_t seed, uint32_t stream, int maxiter, double tol,
+                                 double* w_null, double* stat, double* score, double* w_alt, int32_t* count_ge, int32_t* count_zero, int8_t* status,
+                                 int64_t* iters, double* rep_stat)
+{
+    if (!ctx) return MMM_ERR_ARG;
+    MMM_HIP(ctx, hipSetDevice(ctx->device));
+    MMM_CHECK(ctx, C >= 1 && V >= 1 && D >= 0 && T >= 1 && cat && targets, "mmm_presence_test: NULL argument, D < 0, C < 1, V < 1 or T < 1");
+    if (C > kPrMaxC) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_presence_test: C = %d catalogue signatures (limit %d)", C, kPrMaxC);
+    if (V > kPrMaxV)
+        return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_presence_test: V = %d terms; a block keeps the thresholds and its waves' count vectors in LDS, which holds at most V = %d", V, kPrMaxV);
+    MMM_CHECK(ctx, maxiter >= 1 && tol >= 0.0, "mmm_presence_test: maxiter = %d (>= 1), tol = %g (>= 0)", maxiter, tol);
+    MMM_CHECK(ctx, B >= 0 && b0 >= 0, "mmm_presence_test: B < 0 or b0 < 0");
+    MMM_CHECK(ctx, (int64_t)b0 + (int64_t)B <= (int64_t)INT32_MAX, "mmm_presence_test: b0 + B exceeds 2^31 - 1");
+    if ((int64_t)T * (int64_t)D >= ((int64_t)1 << 31))
+        return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_presence_test: T D = %lld items (limit 2^31 - 1: the item is a 32-bit counter word)", (long long)T * D);
+    for (int i = 0; i < T; ++i) MMM_CHECK(ctx, targets[i] >= 0 && targets[i] < C, "mmm_presence_test: targets[%d] = %d is no row of the catalogue (C = %d)", i, targets[i], C);
+    if (int rc = mmm_check_csr(ctx, "mmm_presence_test", D, V, doc_ptr, term, count)) return rc;
+    std::vector<int32_t> n_doc((size_t)D);
+    for (int d = 0; d < D; ++d) {
+        uint64_t s = 0;
+        for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) {
+            s += (uint64_t)count[e];
+            if (s >= ((uint64_t)1 << 31))
+                return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_presence_test: document %d holds 2^31 or more counts (a draw's index is a 32-bit word: N_d < 2^31)", d);
+        }
+        n_doc[(size_t)d] = (int32_t)s;
+    }
+    // P[c][v] = cat[c][v] / sum_v cat[c][v], the sum in index order (mmm_refit_exposures' P)
+    std::vector<double> P((size_t)C * V);
+    for (int c = 0; c < C; ++c) {
+        double s = 0.0;
+        for (int v = 0; v < V; ++v) {
+            const double x = cat[(size_t)c * V + v];
+            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "mmm_presence_test: catalogue entry (%d, %d) is negative or not finite", c, v);
+            s += x;
+        }
+        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "mmm_presence_test: catalogue row %d sums to %g", c, s);
+        for (int v = 0; v < V; ++v) P[(size_t)c * V + v] = cat[(size_t)c * V + v] / s;
+    }
+    if (D == 0) return MMM_OK;
+    MMM_CHECK(ctx, w_null && stat && score && w_alt && count_ge && count_zero && status && iters, "mmm_presence_test: NULL output");
+    const int64_t nnz = doc_ptr[D];
+    const size_t TD = (size_t)T * (size_t)D, TDC = TD * (size_t)C, DC = (size_t)D * C;
+    const bool want_rep = rep_stat && B > 0;
+
+    const int Cp = (C + 63) & ~63, cus = std::max(1, ctx->num_cu);
+    const int wd = pr_wave_doubles(Cp, V);
+    const size_t pw = sizeof(double) * (size_t)wd;
+
+    DevBuf<int64_t> dp; DevBuf<int32_t> tc, tg, nd, cnt, itm; DevBuf<double> Pd, outd, rep; DevBuf<uint8_t> alw; DevBuf<int8_t> st; DevBuf<unsigned long long> its;
+    DevBuf<int> counter;
+    MMM_HIP(ctx, dp.alloc((size_t)D + 1)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, tg.alloc((size_t)T)); MMM_HIP(ctx, nd.alloc((size_t)D));
+    MMM_HIP(ctx, Pd.alloc(P.size())); MMM_HIP(ctx, outd.alloc(TDC + 3 * TD)); MMM_HIP(ctx, st.alloc(TD)); MMM_HIP(ctx, its.alloc(TD));
+    MMM_HIP(ctx, cnt.alloc(2 * TD)); MMM_HIP(ctx, counter.alloc(1));
+    if (allowed) MMM_HIP(ctx, alw.alloc(DC));
+    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz) {
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    MMM_HIP(ctx, hipMemcpyAsync(tg.p, targets, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, ctx->stream));
+    MMM_HIP(ctx, hipMemcpyAsync(nd.p, n_doc.data(), sizeof(int32_t) * (size_t)D, hipMemcpyHostToDevice, ctx->stream));
+    MMM_HIP(ctx, hipMemcpyAsync(Pd.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (allowed) MMM_HIP(ctx, hipMemcpyAsync(alw.p, allowed, DC, hipMemcpyHostToDevice, ctx->stream));
+    // what an untestable item and an item without replicates leave behind
+    MMM_HIP(ctx, hipMemsetAsync(outd.p, 0, sizeof(double) * outd.n, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(st.p, 0, TD, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(its.p, 0, sizeof(unsigned long long) * TD, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * 2 * TD, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(counter.p, 0, sizeof(int), ctx->stream));
+
+    PrArgs a{};
+    a.D = D; a.C = C; a.V = V; a.Cp = Cp; a.T = T; a.maxiter = maxiter; a.tol = tol;
+    a.doc_ptr = dp.p; a.term = tc.p; a.count = tc.p + nnz; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.targets = tg.p;
+    a.w_null = outd.p; a.stat = outd.p + TDC; a.score = a.stat + TD; a.w_alt = a.score + TD; a.status = st.p; a.iters = its.p; a.counter = counter.p;
+    a.n_doc = nd.p; a.B = B; a.b0 = (uint32_t)b0; a.k0 = (uint32_t)(seed & 0xffffffffull); a.k1 = (uint32_t)(seed >> 32); a.stream = stream;
+    a.count_ge = cnt.p; a.count_zero = cnt.p + TD; a.wave_doubles = wd;
+
+    // ---- observed phase: as many waves per block as their buffers leave room for; few items: fewer, so that they spread over the CUs
+    {
+        int nw = kPrMaxWaves;
+        while (nw > 1 && nw * pw > kPrLdsBlock) nw >>= 1;
+        while (nw > 1 && ((int64_t)TD + nw - 1) / nw < cus) nw >>= 1;
+        const size_t lds = nw * pw;
+        const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(kPrMaxWaves / nw, (int64_t)(kPrLdsBlock / lds)));
+        const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)TD + nw - 1) / nw, (int64_t)cus * per_cu);
+        if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)k_presence_obs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_presence_obs, dim3(grid), dim3(64 * nw), lds, ctx->stream, a);
+        MMM_LAUNCH_CHECK(ctx);
+    }
+    // the statuses come back: the host lists the items that take replicates (a T D-byte copy; the list could be compacted on the device, but
+    // the host needs the statuses anyway to fill the counts of the items that take none)
+    std::vector<int8_t> hst(TD);
+    MMM_HIP(ctx, hipMemcpyAsync(hst.data(), st.p, TD, hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+
+    // ---- replicate phase
+    std::vector<int32_t> staged, direct;
+    if (B > 0) {
+        int P2 = 4;
+        while (P2 < V) P2 <<= 1;
+        const size_t fixed = 16 + sizeof(uint32_t) * (size_t)P2;
+        std::vector<int> n1((size_t)TD, 0);
+        int max_n1 = 0;
+        size_t n_items = 0;
+        for (size_t j = 0; j < TD; ++j) {
+            if (hst[j] != 0) continue;
+            const int d = (int)(j % (size_t)D), t = targets[j / (size_t)D];
+            int n = C;
+            if (allowed) {
+                n = 0;
+                for (int c = 0; c < C; ++c) n += allowed[(size_t)d * C + c] != 0 || c == t;
+            }
+            n1[j] = n; max_n1 = std::max(max_n1, n); ++n_items;
+        }
+        if (n_items) {
+            int nw = 1;
+            for (int t = kPrMaxWaves; t >= 1; t >>= 1)
+                if (fixed + t * pw <= kPrLdsBlock) { nw = t; break; }
+            // rows of P a block can stage beside nw waves' buffers (one double may pad the rows to 16 bytes)
+            auto cap = [&](int t) { const size_t room = (kPrLdsBlock - fixed - t * pw) / sizeof(double); return room ? (int)((room - 1) / (size_t)V) : 0; };
+            int rows_cap = 0;
+            if (!mmm_off(ctx->tune, MMM_OFF_REFIT_LDS)) {
+                if (nw == kPrMaxWaves && cap(nw) < max_n1 && cap(nw / 2) >= max_n1) nw >>= 1;       // four waves with every item's rows in LDS beat eight through L2
+                rows_cap = cap(nw);
+            }
+            int rows = 0;
+            for (size_t j = 0; j < TD; ++j) {
+                if (hst[j] != 0) continue;
+                if (n1[j] <= rows_cap) { staged.push_back((int32_t)j); rows = std::max(rows, n1[j]); }
+                else direct.push_back((int32_t)j);
+            }
+            std::vector<int32_t> all(staged);
+            all.insert(all.end(), direct.begin(), direct.end());
+            MMM_HIP(ctx, itm.alloc(all.size()));
+            MMM_HIP(ctx, hipMemcpyAsync(itm.p, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice, ctx->stream));
+            if (want_rep) {
+                MMM_HIP(ctx, rep.alloc((size_t)B * TD));
+                MMM_HIP(ctx, hipMemsetAsync(rep.p, 0, sizeof(double) * (size_t)B * TD, ctx->stream));
+            }
+            a.P2 = P2; a.rep = want_rep ? rep.p : nullptr;
+            for (int part = 0; part < 2; ++part) {
+                const size_t n = part ? direct.size() : staged.size();
+                if (!n) continue;
+                // replicates per block: one per wave, more while the launch still covers the device several times over (a block's set-up is
+                // shared by its replicates); the geometry cannot change a bit of the output
+                int rpb = nw;
+                while (rpb < B && (int64_t)n * ((B + 2 * rpb - 1) / (2 * rpb)) >= 8ll * cus) rpb *= 2;
+                while ((B + rpb - 1) / rpb > 65535) rpb *= 2;
+                a.items = itm.p + (part ? staged.size() : 0);
+                a.reps_per_block = rpb;
+                a.stage_doubles = part ? 0 : (int)(((size_t)rows * V + 1) & ~(size_t)1);
+                const size_t lds = fixed + sizeof(double) * (size_t)a.stage_doubles + nw * pw;
+                auto kern = part ? k_presence_rep<false> : k_presence_rep<true>;
+                if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(kern, dim3((unsigned)n, (unsigned)((B + rpb - 1) / rpb)), dim3(64 * nw), lds, ctx->stream, a);
+                MMM_LAUNCH_CHECK(ctx);
+            }
+        }
+    }
+    // staged on the host so that a failing copy leaves the caller's arrays as they were
+    std::vector<double> ho(TDC + 3 * TD), hr(want_rep && rep.p ? (size_t)B * TD : 0);
+    std::vector<int32_t> hc(2 * TD);
+    std::vector<unsigned long long> hi(TD);
+    MMM_HIP(ctx, hipMemcpyAsync(ho.data(), outd.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipMemcpyAsync(hc.data(), cnt.p, sizeof(int32_t) * hc.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipMemcpyAsync(hi.data(), its.p, sizeof(unsigned long long) * TD, hipMemcpyDeviceToHost, ctx->stream));
+    if (hr.size()) MMM_HIP(ctx, hipMemcpyAsync(hr.data(), rep.p, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MMM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(w_null, ho.data(), sizeof(double) * TDC);
+    memcpy(stat, ho.data() + TDC, sizeof(double) * TD); memcpy(score, ho.data() + TDC + TD, sizeof(double) * TD);
+    memcpy(w_alt, ho.data() + TDC + 2 * TD, sizeof(double) * TD);
+    memcpy(status, hst.data(), TD);
+    for (size_t j = 0; j < TD; ++j) {
+        count_ge[j] = hst[j] == 1 ? B : hc[j];            // statistic 0: every replicate is at least as large, and none is run
+        count_zero[j] = hc[TD + j];
+        iters[j] = (int64_t)hi[j];
+    }
+    if (want_rep) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (int b = 0; b < B; ++b)
+            for (size_t j = 0; j < TD; ++j) rep_stat[(size_t)b * TD + j] = hst[j] == 0 ? hr[(size_t)b * TD + j] : nan;
+    }
+    return MMM_OK;
+}

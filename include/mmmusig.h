@@ -96,7 +96,8 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
     MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
     MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
-    MMM_OFF_ALL = (1 << 16) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
+    MMM_OFF_DECOMPOSE_LDS = 1 << 16,     /* mmm_decompose_search, mmm_signature_decompose: read G and b through L2 even where they fit LDS; same bits                        */
+    MMM_OFF_ALL = (1 << 17) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
 typedef struct {
     int lda_build;        /* MMM_BUILD_*: E-step build of LDA / ILDA handles                                                              */
@@ -633,6 +634,41 @@ int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr,
                       const uint8_t* allowed /* [D][C] or NULL */, int T, const int32_t* targets /* [T] */, int B, int b0, uint64_t seed, uint32_t stream,
                       int maxiter, double tol, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */, int32_t* count_ge,
                       int32_t* count_zero, int8_t* status, int64_t* iters, double* rep_stat /* [B][T D] or NULL */);
+
+/* ---- signatures as sparse non-negative mixtures of catalogue rows: for every size s <= S the best subset of exactly s rows, by exhaustive
+ * search (the step between extraction and assignment; no counterpart in the reference).
+ * n signatures sig [n][V] and a catalogue cat [C][V], every entry finite and >= 0; rows need not be normalised.
+ * Stage 1, moments.  G[c][c'] = sum_v cat[c][v] cat[c'][v];  b[i][c] = sum_v sig[i][v] cat[c][v];  ss[i] = sum_v sig[i][v]^2.  Each sum in
+ *   the order of mmm_signature_cosine's sums: 64 partial sums, partial l over v = l, l + 64, ... ascending from 0.0, combined inside the 16-lane
+ *   rows as l with l ^ 1, ^ 2, the other quad pair, the other half, then the rows as (row 0 + row 2) + (row 1 + row 3).  Products and sums are
+ *   separate roundings.  G is symmetric by construction: the entries c <= c' are computed and written to both places.
+ * Stage 2, search, on (G, b, ss) alone.  For a subset c_1 < ... < c_s with g_ij = G[c_i][c_j] and beta_i = b[c_i], row by row for i = 0 .. s-1
+ *   (every product, difference and reciprocal one IEEE rounding):
+ *     u_ij = g_ij - sum_{p<j} u_ip l_jp for j < i, sequentially with p ascending: ((g - t_0) - t_1) - ...;   l_ij = u_ij r_j;
+ *     d_i = g_ii - sum_{p<i} u_ip l_ip;   r_i = 1 / d_i (one correctly rounded division per pivot, the only division);
+ *     y_i = beta_i - sum_{p<i} l_ip y_p;   z_i = y_i r_i;
+ *   gain = sum_i y_i z_i, i ascending, starting from y_0 z_0;  then for i = s-1 .. 0:  w_i = z_i - sum_{p>i} l_pi w_p, p ascending.
+ *   Row i uses the rows before it only, so two subsets with a common prefix share its numbers bit for bit.
+ *   The subset is ADMISSIBLE when every d_i > 2^-26 g_ii (otherwise row c_i lies in the span of the earlier ones: a duplicated or scaled
+ *   catalogue row, an exact blend) and every w_i > 0.  best[s] = the admissible subset of size EXACTLY s with the largest gain, ties to the
+ *   lexicographically smallest (c_1, ..., c_s): the maximum of a total order, independent of the order in which subsets are visited or reduced.
+ *   A weight of an NNLS solution that is 0 makes it the solution on a smaller subset, which is enumerated too: the best non-negative
+ *   reconstruction with AT MOST s rows is the running maximum of gain over the sizes <= s, its squared residual ss - gain and its cosine to
+ *   the signature sqrt(gain / ss).
+ * Outputs per (i, s), s = 1 .. S:  subset[(i S + s-1) S + j] (j < S; -1 beyond the s members), weight likewise (0 beyond), gain[i S + s-1],
+ *   cosine[i S + s-1] = sqrt(min(gain / ss, 1)).  No admissible subset of size s, ss = 0 or s > C: subset -1, weight 0, gain 0, cosine 0.
+ *   The same arguments give the same bits on every run, whatever n and wherever G and b are held (LDS, or read through L2 when C > 128).
+ * Limits: 1 <= S <= 6, 1 <= C <= 256, binom(C, min(S, C)) < 2^32, V >= 1, n >= 0 (n = 0 computes the moments asked for and nothing else).
+ *   MMM_ERR_UNSUPPORTED, with the limit in the message: S > 6, C > 256, binom(C, min(S, C)) >= 2^32.  MMM_ERR_ARG: NULL pointers, S < 1, C < 1,
+ *   n < 0, V < 1, a negative or non-finite entry of sig or cat, a catalogue row that is all zero.  Moments that are not finite (caller-supplied,
+ *   or finite inputs whose products overflow) or ss < 0: an entry of G marks every signature, one of b[i] or ss[i] marks signature i; a marked
+ *   signature comes out empty (subset -1), the others are computed, and the call returns MMM_ERR_ARG naming the first.
+ *   No collective: on a multi-rank context both act on the arrays they are given. */
+int mmm_decompose_search(mmm_ctx* ctx, int n, int C, int S, const double* G /* [C][C] */, const double* b /* [n][C] */, const double* ss /* [n] */,
+                         int32_t* subset /* [n][S][S] */, double* weight /* [n][S][S] */, double* gain /* [n][S] */, double* cosine /* [n][S] */);
+/* Stage 1 on the device, then stage 2 on its moments.  G_out [C][C], b_out [n][C], ss_out [n]: the moments, each may be NULL. */
+int mmm_signature_decompose(mmm_ctx* ctx, int n, int C, int V, const double* sig, const double* cat, int S, int32_t* subset, double* weight, double* gain,
+                            double* cosine, double* G_out, double* b_out, double* ss_out);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,8 @@ _SIGS = {
     "mmm_fit_check": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "mmm_presence_test": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int,
                                     C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_decompose_search": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_signature_decompose": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 
@@ -190,7 +192,7 @@ class TuningOpts(C.Structure):
 
 BUILDS = {"auto": 0, "sparse": 1, "dense": 2, "wide": 3}
 OFF = {"lda_padded_rows": 1 << 0, "lda_count_rows": 1 << 1, "lda_rows16": 1 << 2, "lda_ll_join": 1 << 3, "lda_merged": 1 << 4, "p2p_folded": 1 << 5,
-       "ctm_packed": 1 << 6, "ctm_cpl": 1 << 7, "ctm_kfit": 1 << 8, "ctm_fused_gauss": 1 << 9, "ctm_ll_rows": 1 << 10, "lda_early_prologue": 1 << 11, "ctm_pipe_gauss": 1 << 12, "ctm_solve_order": 1 << 13, "lda_block_stats": 1 << 14, "refit_lds": 1 << 15}
+       "ctm_packed": 1 << 6, "ctm_cpl": 1 << 7, "ctm_kfit": 1 << 8, "ctm_fused_gauss": 1 << 9, "ctm_ll_rows": 1 << 10, "lda_early_prologue": 1 << 11, "ctm_pipe_gauss": 1 << 12, "ctm_solve_order": 1 << 13, "lda_block_stats": 1 << 14, "refit_lds": 1 << 15, "decompose_lds": 1 << 16}
 
 
 class Context:

@@ -213,6 +213,17 @@ __device__ __forceinline__ double rows_sum4(double x)
     return __hiloint2double((int)b.x, (int)a.x) + __hiloint2double((int)b.y, (int)a.y);
 }
 
+// sum over the 64 lanes, valid in every lane, in ONE fixed order (the sums of match.hip and decompose.hip are defined by it): inside the
+// 16-lane rows by DPP (lane ^ 1, lane ^ 2, the other quad pair, the other half), then the rows as (row 0 + row 2) + (row 1 + row 3)
+__device__ __forceinline__ double wave_sum_fixed(double v)
+{
+    v += dpp_mov_f64<0xB1>(v);
+    v += dpp_mov_f64<0x4E>(v);
+    v += dpp_mov_f64<0x141>(v);
+    v += dpp_mov_f64<0x140>(v);
+    return rows_sum4(v);
+}
+
 __device__ __forceinline__ double wave_max_dpp(double v)
 {
     v = fmax(v, dpp_mov_f64<0xB1>(v));

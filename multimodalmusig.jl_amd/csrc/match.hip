@@ -20,17 +20,7 @@ constexpr size_t kMatchUpBudget = (size_t)1 << 24;   // doubles of caller signat
 
 static_assert(kCosCT % kCosWaves == 0 && kCosVC % 64 == 0 && kCosCT <= 64, "tile shape");
 
-// sum over the 64 lanes, valid in every lane: inside the 16-lane rows by DPP (lane ^ 1, lane ^ 2, the other quad pair, the other half), then
-// the rows as (row 0 + row 2) + (row 1 + row 3)
-__device__ __forceinline__ double wave_sum_fixed(double v)
-{
-    v += dpp_mov_f64<0xB1>(v);
-    v += dpp_mov_f64<0x4E>(v);
-    v += dpp_mov_f64<0x141>(v);
-    v += dpp_mov_f64<0x140>(v);
-    return rows_sum4(v);
-}
-
+// (wave_sum_fixed, the one order of every cross-lane sum here, is in dev_math.h: decompose.hip shares it)
 // Element (k, v) of replica r is sig[r][k * sk + v * sv]; catalogue row c is cat[c * ck + v * cv].  grid (ceil(K / kCosWaves), R).
 // A wave takes one signature and walks the catalogue in tiles of kCosCT rows; the block stages a tile kCosVC terms at a time in LDS.  Lane l
 // owns the terms l, l + 64, ... (ascending), so with sv = 1 (both handle layouts and the array form) a wave's loads are contiguous.

@@ -670,6 +670,53 @@ int mmm_decompose_search(mmm_ctx* ctx, int n, int C, int S, const double* G /* [
 int mmm_signature_decompose(mmm_ctx* ctx, int n, int C, int V, const double* sig, const double* cat, int S, int32_t* subset, double* weight, double* gain,
                             double* cosine, double* G_out, double* b_out, double* ss_out);
 
+/* ---- new signatures beside a FIXED catalogue: the F catalogue rows are held, J free rows are learned, R restarts in one call ("fit and
+ * extract"; F = 0 is plain KL-NMF / pLSA extraction, J = 0 the plain refit; no counterpart in the reference).
+ * CSR corpus of D documents over V terms and cat [F][V] as mmm_refit_exposures takes them, with its checks and its index-order normalisation to
+ * P (F = 0: cat may be NULL); allowed [D][F] or NULL = all (the free rows are always allowed); K = F + J rows in all, the fixed ones first.
+ * n_dv, N_d, f_dv = n_dv / N_d, the 64 `partials` (partial l over the indices l, l + 64, ... ascending from 0.0), the `butterfly` that combines
+ * them (l with l ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1) and the mixture, sequential over the rows ascending, are those of mmm_refit_exposures.
+ * Start of restart r (GLOBAL index r0 + r).  Rows 0 .. F-1 of P are the normalised catalogue, row F + j is the free row Q_j:
+ *   from init [R][J][V]: entries finite and >= 0, every row sum > 0, each row divided by its sum in index order;
+ *   init == NULL: Q0_jv = (u + 1) 2^-32 (exact in a double), u being output word v % 4 of the Philox4x32-10 block with the constants and the key
+ *   (seed low 32 bits, seed high 32 bits) of mmm_resample_counts and the counter (v / 4, 0x80000000 | j, r0 + r, stream); Q0_j is then divided by
+ *   its sequential sum over v.  mmm_resample_counts, mmm_split_counts, mmm_simulate_counts and mmm_presence_test all put a document or item
+ *   index in the second counter word, an int >= 0 and so below 2^31: a start shares no random word with any of them, whatever the stream.
+ *   A_d = the allowed fixed rows and all free rows; w_dk = 1 / |A_d| on A_d, 0 elsewhere.  A document with N_d = 0 or an empty A_d keeps w = 0
+ *   and enters no sum.
+ * Iteration t = 1 .. maxiter, all documents jointly:
+ *   q_dv = sum_k w_dk P_kv, k ascending;  r_dv = f_dv / q_dv where n_dv > 0 and q_dv > 0, else 0;  g_dk = butterfly(partials(r_d. o P_k.));
+ *   w'_dk = w_dk g_dk.
+ *   Free rows, with a_dj = N_d w_d,F+j (the OLD w):  s_jv = sum_d a_dj r_dv, every product rounded, then added, in this order: document d
+ *   belongs to stripe d mod 16; a stripe's sum runs over its documents in ascending d from 0.0; the 16 stripe sums are then added in ascending
+ *   stripe order from 0.0.  t_jv = Q_jv s_jv;  z_j = butterfly(partials(t_j.));  Q'_jv = t_jv / z_j if z_j > 0, else Q_jv.
+ *   Stop after an iteration with max(max_dk |w' - w|, max_jv |Q' - Q|) < tol (strict: tol = 0 runs maxiter iterations).
+ * Finish, per document as fit(A) of mmm_refit_exposures: w_d <- w_d / S_d if S_d > 0, S_d the sequential sum over k; q recomputed;
+ *   ll_doc = sum over n_dv > 0, q_dv > 0 of n_dv log q_dv (partials and butterfly); unexplained = sum over n_dv > 0, q_dv = 0 of n_dv (N_d
+ *   for a document that entered no sum, whose other outputs are 0); ll[r] = sum_d ll_doc in stripe order (as s_jv).
+ * Products, sums and the (IEEE, correctly rounded) divisions are separate roundings.  All terms are >= 0, so padding, a zero weight and an
+ *   absent document change no bit.  The stripe count 16 belongs to the definition, not to the launch: every launch geometry (`waves`, the
+ *   number of restarts in flight, w held in LDS or in memory) gives the same bits, and so does every run.  Only +, x, / and comparisons decide
+ *   sig, w, iters and unexplained; log (the device library's, < 1 ulp) enters ll and ll_doc only.
+ * Consequences.  (a) J = 0, tol = 0: w, ll_doc and unexplained of every document are those of mmm_refit_exposures with penalty = NULL and the
+ *   same maxiter (with tol > 0 the refit stops per document, this per restart).  (b) A call with (r0, R) is a slice of the call with
+ *   (0, r0 + R) (with init: of its rows).  (c) F = 0: multiplicative KL-NMF / pLSA with normalised rows.
+ * Outputs: sig [R][J][V] the free rows; w [R][D][K] the normalised weights (or NULL); ll [R]; ll_doc, unexplained [R][D] (or NULL);
+ *   iters [R] the iterations run.  waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, else 1, 2, 4, 8 or 16).
+ * Limits: 1 <= K <= 256, J <= 32, V >= 1, D K < 2^31, D V < 2^31, r0 + R <= 2^31 - 1; P and one r vector per wave are held in LDS:
+ *   8 (K V + waves V) + 4 K + 392 bytes may not exceed 160 KiB (the library's choice, 16 waves for K <= 16 and 8 beyond, halves the waves until they fit).  One block
+ *   runs a restart: a call with few restarts and very many documents uses few CUs.
+ * MMM_ERR_ARG, nothing written: NULL pointers (ctx, cat with F > 0, sig with J > 0, ll, iters, the CSR arrays), D < 0, F < 0, J < 0, K < 1,
+ *   V < 1, R < 0, r0 < 0, r0 + R > 2^31 - 1, maxiter < 1, tol < 0 or NaN, waves not one of 0, 1, 2, 4, 8, 16, an init entry that is negative
+ *   or not finite, an init row whose sum is 0, and the catalogue and corpus errors of mmm_refit_exposures.  MMM_ERR_UNSUPPORTED, with the limit
+ *   in the message: K > 256, J > 32, D K or D V >= 2^31, more LDS than a block may take.  D = 0 or R = 0: MMM_OK, nothing written.  No
+ *   collective: on a multi-rank context it acts on its arrays. */
+int mmm_extract_signatures(mmm_ctx* ctx, int D, int F, int J, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count,
+                           const double* cat /* [F][V] or NULL if F = 0 */, const uint8_t* allowed /* [D][F] or NULL */, int R, int r0, uint64_t seed,
+                           uint32_t stream, const double* init /* [R][J][V] or NULL */, int maxiter, double tol, int waves, double* sig /* [R][J][V] */,
+                           double* w /* [R][D][K] or NULL */, double* ll /* [R] */, double* ll_doc, double* unexplained /* [R][D] or NULL */,
+                           int32_t* iters /* [R] */);
+
 #ifdef __cplusplus
 }
 #endif

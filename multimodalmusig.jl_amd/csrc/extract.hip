@@ -13,7 +13,7 @@
 // w [D][K] too where it fits; n and f are densified once per call into [D][V] arrays that every block reads through L2.
 #include "mmm_internal.h"
 #include "dev_math.h"
-#include "refit_reduce.cuh"
+#include "mixture_fit.cuh"
 #include "mmm_philox.h"
 
 namespace {
@@ -103,20 +103,7 @@ __device__ __forceinline__ double ex_document(const ExArgs& a, const double* __r
             for (int v = lane; v < V; v += 64) sl[(size_t)j * V + v] += aj * rb[v];
         }
     }
-    double md = 0.0;
-    for (int b = 0; b < K; b += 32) {
-        const int m = min(32, K - b);
-        double g; int j;
-        if (m <= 4) { g = rf_gchunk<2>(P, ident + b, rb, V, lane); j = lane >> 4; }
-        else if (m <= 8) { g = rf_gchunk<3>(P, ident + b, rb, V, lane); j = lane >> 3; }
-        else if (m <= 16) { g = rf_gchunk<4>(P, ident + b, rb, V, lane); j = lane >> 2; }
-        else { g = rf_gchunk<5>(P, ident + b, rb, V, lane); j = lane >> 1; }
-        if (j < m) {
-            const double wo = wd[b + j], wn = wo * g;
-            md = fmax(md, fabs(wn - wo));
-            wd[b + j] = wn;           // the lanes that share j write the same bits
-        }
-    }
+    const double md = rf_update_weights(P, ident, wd, K, rb, V, lane);
     rf_wave_sync();
     return md;
 }
@@ -299,18 +286,8 @@ extern "C" int mmm_extract_signatures(mmm_ctx* ctx, int D, int F, int J, int V, 
     MMM_CHECK(ctx, waves == 0 || waves == 1 || waves == 2 || waves == 4 || waves == 8 || waves == 16, "mmm_extract_signatures: waves = %d (0, 1, 2, 4, 8 or 16)", waves);
     MMM_CHECK(ctx, (F == 0 || cat) && (D == 0 || R == 0 || ((J == 0 || sig) && ll && iters)), "mmm_extract_signatures: NULL argument");
     if (int rc = mmm_check_csr(ctx, "mmm_extract_signatures", D, V, doc_ptr, term, count)) return rc;
-    // P[c][v] = cat[c][v] / sum_v cat[c][v], the sum in index order
-    std::vector<double> P((size_t)F * V);
-    for (int c = 0; c < F; ++c) {
-        double s = 0.0;
-        for (int v = 0; v < V; ++v) {
-            const double x = cat[(size_t)c * V + v];
-            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "mmm_extract_signatures: catalogue entry (%d, %d) is negative or not finite", c, v);
-            s += x;
-        }
-        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "mmm_extract_signatures: catalogue row %d sums to %g", c, s);
-        for (int v = 0; v < V; ++v) P[(size_t)c * V + v] = cat[(size_t)c * V + v] / s;
-    }
+    std::vector<double> P;           // the fixed rows normalised: mmm_refit_exposures' P
+    if (int rc = mmm_normalise_rows(ctx, "mmm_extract_signatures", F, V, cat, P)) return rc;
     const size_t JV = (size_t)J * V;
     std::vector<double> Q0;
     if (init && J) {
@@ -353,27 +330,22 @@ extern "C" int mmm_extract_signatures(mmm_ctx* ctx, int D, int F, int J, int V, 
         dn[d] = N;
         dn[(size_t)D + d] = (N > 0.0 && na > 0) ? 1.0 / (double)na : 0.0;
     }
-    const int64_t nnz = doc_ptr[D];
     const size_t RD = (size_t)R * D;
-    DevBuf<int64_t> dp; DevBuf<int32_t> tc, itd; DevBuf<double> Pd, q0d, nf, dnd, slab, wws, outd; DevBuf<uint8_t> alw; DevBuf<int> counter;
-    MMM_HIP(ctx, dp.alloc((size_t)D + 1)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, Pd.alloc(P.size())); MMM_HIP(ctx, nf.alloc(2 * DV));
+    DevCsr csr; DevBuf<int32_t> itd; DevBuf<double> Pd, q0d, nf, dnd, slab, wws, outd; DevBuf<uint8_t> alw; DevBuf<int> counter;
+    MMM_HIP(ctx, Pd.alloc(P.size())); MMM_HIP(ctx, nf.alloc(2 * DV));
     MMM_HIP(ctx, dnd.alloc(dn.size())); MMM_HIP(ctx, slab.alloc((size_t)grid * kExStripes * JV)); MMM_HIP(ctx, counter.alloc(1)); MMM_HIP(ctx, itd.alloc((size_t)R));
     MMM_HIP(ctx, outd.alloc((size_t)R * JV + (size_t)R + (w ? RD * K : 0) + (ll_doc ? RD : 0) + (unexplained ? RD : 0)));
     if (!Q0.empty()) MMM_HIP(ctx, q0d.alloc(Q0.size()));
     if (allowed && F) MMM_HIP(ctx, alw.alloc((size_t)D * F));
     if (!w_lds) MMM_HIP(ctx, wws.alloc((size_t)grid * DK));
-    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (int rc = csr.upload(ctx, D, doc_ptr, term, count)) return rc;
     if (F) MMM_HIP(ctx, hipMemcpyAsync(Pd.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice, ctx->stream));
     if (!Q0.empty()) MMM_HIP(ctx, hipMemcpyAsync(q0d.p, Q0.data(), sizeof(double) * Q0.size(), hipMemcpyHostToDevice, ctx->stream));
     MMM_HIP(ctx, hipMemcpyAsync(dnd.p, dn.data(), sizeof(double) * dn.size(), hipMemcpyHostToDevice, ctx->stream));
     if (allowed && F) MMM_HIP(ctx, hipMemcpyAsync(alw.p, allowed, (size_t)D * F, hipMemcpyHostToDevice, ctx->stream));
     MMM_HIP(ctx, hipMemsetAsync(nf.p, 0, sizeof(double) * DV, ctx->stream));
     MMM_HIP(ctx, hipMemsetAsync(counter.p, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)((D + 3) / 4)), dim3(256), 0, ctx->stream, D, V, dp.p, tc.p, tc.p + nnz, nf.p);
+    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)((D + 3) / 4)), dim3(256), 0, ctx->stream, D, V, csr.ptr, csr.term, csr.count, nf.p);
     MMM_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_extract_freq, dim3((unsigned)((DV + 255) / 256)), dim3(256), 0, ctx->stream, DV, V, nf.p, dnd.p, nf.p + DV);
     MMM_LAUNCH_CHECK(ctx);

@@ -23,6 +23,49 @@ int mmm_check_csr(mmm_ctx* ctx, const char* who, int D, int V, const int64_t* do
     return MMM_OK;
 }
 
+int mmm_doc_totals(mmm_ctx* ctx, const char* who, int D, const int64_t* doc_ptr, const int32_t* count, int32_t* n_doc)
+{
+    for (int d = 0; d < D; ++d) {
+        uint64_t s = 0;
+        for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) {
+            s += (uint64_t)count[e];
+            if (s >= ((uint64_t)1 << 31))
+                return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "%s: document %d holds 2^31 or more counts (a draw's index is a 32-bit word: N_d < 2^31)", who, d);
+        }
+        n_doc[d] = (int32_t)s;
+    }
+    return MMM_OK;
+}
+
+int mmm_normalise_rows(mmm_ctx* ctx, const char* who, int rows, int V, const double* src, std::vector<double>& dst)
+{
+    dst.resize((size_t)rows * V);
+    for (int c = 0; c < rows; ++c) {
+        double s = 0.0;
+        for (int v = 0; v < V; ++v) {
+            const double x = src[(size_t)c * V + v];
+            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "%s: catalogue entry (%d, %d) is negative or not finite", who, c, v);
+            s += x;
+        }
+        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "%s: catalogue row %d sums to %g", who, c, s);
+        for (int v = 0; v < V; ++v) dst[(size_t)c * V + v] = src[(size_t)c * V + v] / s;
+    }
+    return MMM_OK;
+}
+
+int DevCsr::upload(mmm_ctx* ctx, int D, const int64_t* h_ptr, const int32_t* h_term, const int32_t* h_count, size_t extra_i64)
+{
+    nnz = h_ptr[D];
+    MMM_HIP(ctx, dp.alloc((size_t)D + 1 + extra_i64)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz));
+    MMM_HIP(ctx, hipMemcpyAsync(dp.p, h_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz) {
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p, h_term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, h_count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    ptr = dp.p; term = tc.p; count = tc.p + nnz;
+    return MMM_OK;
+}
+
 namespace {
 
 // mode 0: λ_objective(x = λ, other = ν, c = Ndivζ, sumθ, μ, S = invΣ);  mode 1: ν_objective(x = ν, other = λ, c, μ unused, S)
@@ -123,15 +166,10 @@ __global__ __launch_bounds__(256) void k_free_loglik_total(int D, const double* 
 int loglik_from_tables(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* props_dev,
                        const double* phi_dev, double* ll)
 {
-    const int64_t nnz = doc_ptr[D];
-    DevBuf<int64_t> dp; DevBuf<int32_t> t, c; DevBuf<double> tmp;
-    MMM_HIP(ctx, dp.alloc((size_t)D + 1)); MMM_HIP(ctx, t.alloc((size_t)nnz)); MMM_HIP(ctx, c.alloc((size_t)nnz)); MMM_HIP(ctx, tmp.alloc(2 * (size_t)D + 4));
-    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MMM_HIP(ctx, hipMemcpyAsync(t.p, term, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, ctx->stream));
-        MMM_HIP(ctx, hipMemcpyAsync(c.p, count, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (D) hipLaunchKernelGGL(k_free_loglik_docs, dim3((unsigned)((D + 3) / 4)), dim3(256), 0, ctx->stream, D, K, V, dp.p, t.p, c.p, props_dev, phi_dev, tmp.p, tmp.p + D);
+    DevCsr csr; DevBuf<double> tmp;
+    if (int rc = csr.upload(ctx, D, doc_ptr, term, count)) return rc;
+    MMM_HIP(ctx, tmp.alloc(2 * (size_t)D + 4));
+    if (D) hipLaunchKernelGGL(k_free_loglik_docs, dim3((unsigned)((D + 3) / 4)), dim3(256), 0, ctx->stream, D, K, V, csr.ptr, csr.term, csr.count, props_dev, phi_dev, tmp.p, tmp.p + D);
     hipLaunchKernelGGL(k_free_loglik_total, dim3(1), dim3(256), 0, ctx->stream, D, tmp.p, tmp.p + D, tmp.p + 2 * (size_t)D);
     MMM_LAUNCH_CHECK(ctx);
     MMM_HIP(ctx, hipMemcpyAsync(ll, tmp.p + 2 * (size_t)D, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

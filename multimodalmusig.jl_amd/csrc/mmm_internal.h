@@ -229,6 +229,22 @@ int mmm_consensus_tables(mmm_ctx* ctx, const char* who, int R, int K, int V, con
 // ---- caller CSR arrays (free.hip): doc_ptr from 0 and not decreasing, terms in [0, V), counts >= 0; MMM_ERR_ARG with `who` in the message
 int mmm_check_csr(mmm_ctx* ctx, const char* who, int D, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count);
 
+// n_doc[d] = the counts of document d of a checked CSR; MMM_ERR_UNSUPPORTED where a document holds 2^31 or more (a draw's index is a 32-bit word)
+int mmm_doc_totals(mmm_ctx* ctx, const char* who, int D, const int64_t* doc_ptr, const int32_t* count, int32_t* n_doc);
+
+// dst[r][v] = src[r][v] / sum_v src[r][v], the sum in index order; MMM_ERR_ARG for an entry that is negative or not finite and for a row
+// whose sum is not positive and finite
+int mmm_normalise_rows(mmm_ctx* ctx, const char* who, int rows, int V, const double* src, std::vector<double>& dst);
+
+// a checked CSR on the device, copied on the ctx stream: ptr [D + 1] followed by extra_i64 words the caller owns (dp.p + D + 1), and
+// term | count in one buffer
+struct DevCsr {
+    DevBuf<int64_t> dp; DevBuf<int32_t> tc;
+    const int64_t* ptr = nullptr; const int32_t* term = nullptr; const int32_t* count = nullptr;
+    int64_t nnz = 0;
+    int upload(mmm_ctx* ctx, int D, const int64_t* h_ptr, const int32_t* h_term, const int32_t* h_count, size_t extra_i64 = 0);
+};
+
 // ---- held-out score (select.hip) for mmm_mixture_score and the handle entry of lda.hip.  R replicas; the CSR is the caller's (host, checked here).
 // h_prop[r]: device pointer of replica r's K x D table -- proportions, or with from_gamma the gamma the proportions are formed from
 // (theta = gamma / sum gamma, the expression of the mmm_lda_get(THETA) route); h_phi[r]: device pointer of its [k V + v] table.

@@ -7,11 +7,12 @@
 // the rows of the item's signatures in LDS (where they fit), forms the mixture of the null weights and its integer thresholds exactly as
 // k_simulate does, and then every wave takes one replicate at a time: Philox draws into its own LDS histogram, f = n / N, the null fit,
 // the score, the alternative fit only where the score exceeds 1, one comparison.  The replicate's counts never leave LDS.
-// Lane l owns the terms v = l, l + 64, ...; the sums of fit(A) are those of refit.hip (refit_reduce.cuh), the draw is simulate.hip's.
+// Lane l owns the terms v = l, l + 64, ...; fit(A) is the one refit.hip runs (mixture_fit.cuh), the thresholds and the draw are the ones
+// simulate.hip runs (mmm_philox.h).
 #include "mmm_internal.h"
 #include "dev_math.h"
 #include "mmm_philox.h"
-#include "refit_reduce.cuh"
+#include "mixture_fit.cuh"
 
 namespace {
 
@@ -19,7 +20,6 @@ constexpr int kPrMaxC = 256;
 constexpr int kPrMaxV = 4096;                   // k_simulate's limit: the threshold row and a wave's buffers stay in LDS
 constexpr int kPrMaxWaves = 8;                  // 8 waves of up to 256 VGPRs fill a CU: two per SIMD
 constexpr size_t kPrLdsBlock = 160 * 1024;      // LDS a block may take (the CU's)
-constexpr uint32_t kPrSimBit = 0x80000000u;     // high bit of the third counter word: the words of mmm_simulate_counts
 
 struct PrArgs {
     int D, C, V, Cp, T, maxiter;
@@ -61,33 +61,18 @@ __device__ __forceinline__ PrWave pr_carve(double* base, int Cp, int V)
 // place of t in act1.
 __device__ __forceinline__ int pr_lists(const PrArgs& a, int d, int t, const PrWave& w, int lane, int& tpos)
 {
-    const int C = a.C;
-    int n1 = 0, tp = 0;
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + lane;
-        const bool on = c < C && (c == t || (a.allowed ? a.allowed[(size_t)d * C + c] != 0 : true));
-        const unsigned long long m = __ballot(on);
-        if (on) w.act1[n1 + __popcll(m & ((1ull << lane) - 1ull))] = c;
-        if (c0 == (t & ~63)) tp = n1 + __popcll(m & ((1ull << (t & 63)) - 1ull));
-        n1 += __popcll(m);
-    }
+    const int n1 = rf_active_list(a.allowed ? a.allowed + (size_t)d * a.C : nullptr, a.C, t, w.act1, lane, tpos);
+    rf_list_without(w.act1, w.act0, n1, tpos, lane);
+    rf_pad_list(w.act1, n1, lane);
+    if (n1 > 1) rf_pad_list(w.act0, n1 - 1, lane);
     rf_wave_sync();
-    const int n0 = n1 - 1;
-    for (int i = lane; i < n0; i += 64) w.act0[i] = w.act1[i < tp ? i : i + 1];
-    rf_wave_sync();
-    for (int i = n1 + lane; i < ((n1 + 63) & ~63); i += 64) w.act1[i] = w.act1[0];
-    if (n0 > 0)
-        for (int i = n0 + lane; i < ((n0 + 63) & ~63); i += 64) w.act0[i] = w.act0[0];
-    rf_wave_sync();
-    tpos = tp;
     return n1;
 }
 
 // The statistic of the count vector in w.hist (total N, f_v in w.fb) for the lists w.act0 (n0 >= 1 rows) and w.act1 (n0 + 1 rows, the
-// target at tpos); trow: the target's row of P.  fit(A) is k_refit's, instruction for instruction: the cold start, q_v sequentially over the
-// list, the 64 partial sums of g_c through the transposing butterfly, the normalisation, ll and u.  Pass 0 is the null fit and ends with
-// the score s = sum_v r_v P[t][v] under the normalised null weights (the lane is the partial sum, wave_sum the butterfly); pass 1, the
-// alternative fit, runs only where the definition asks for it.  Leaves the null weights in w.w0 and the alternative ones in w.w1.
+// target at tpos); trow: the target's row of P.  The null fit ends with the score s = sum_v r_v P[t][v] under the normalised null weights,
+// taken in the sweep that takes ll; the alternative fit runs only where the definition asks for it.  Leaves the null weights in w.w0 and
+// the alternative ones in w.w1.
 struct PrStat {
     double lam, s;
     bool alt;
@@ -96,85 +81,25 @@ struct PrStat {
 
 __device__ __forceinline__ PrStat pr_statistic(const double* __restrict__ P, const PrWave& w, int n0, int trow, int V, int lane, int maxiter, double tol)
 {
-    const uint32_t* hist = w.hist;
-    const double* fb = w.fb;
-    double* rb = w.rb;
-    double ll0 = 0.0, u0 = 0.0, ll1 = 0.0, u1 = 0.0, s = 0.0;
-    int iters = 0;
-    bool alt = false;
+    const RfCountsU32 counts{w.hist};
+    RfLoglik f0{}, f1{};
+    PrStat r;
+    r.iters = 0; r.alt = false;
+    // a loop with one call site each, so that a kernel holds the fit and the sweep once (mixture_fit.cuh, rf_loglik, has the reason)
     for (int pass = 0; pass < 2; ++pass) {
-        const int* cact = pass ? w.act1 : w.act0;
+        const int* act = pass ? w.act1 : w.act0;
         double* cw = pass ? w.w1 : w.w0;
-        const int cn = n0 + pass;
-        const double wc = 1.0 / (double)cn;
-        for (int i = lane; i < cn; i += 64) cw[i] = wc;
-        rf_wave_sync();
-        int it = 0;
-        while (it < maxiter) {
-            ++it;
-            // two of the lane's terms at a time: their sums over c are independent chains (each still in the order of c)
-            for (int v = lane; v < V; v += 128) {
-                const bool two = v + 64 < V;
-                const int v1 = two ? v + 64 : v;
-                double q = 0.0, q1 = 0.0;
-#pragma unroll 4
-                for (int i = 0; i < cn; ++i) {
-                    const double wi = cw[i];
-                    const int row = cact[i] * V;
-                    q += wi * P[row + v];
-                    q1 += wi * P[row + v1];
-                }
-                rb[v] = (hist[v] != 0u && q > 0.0) ? fb[v] / q : 0.0;
-                if (two) rb[v1] = (hist[v1] != 0u && q1 > 0.0) ? fb[v1] / q1 : 0.0;
-            }
-            rf_wave_sync();
-            double md = 0.0;
-            for (int b = 0; b < cn; b += 32) {
-                const int m = min(32, cn - b);
-                double g; int j;
-                if (m <= 4) { g = rf_gchunk<2>(P, cact + b, rb, V, lane); j = lane >> 4; }
-                else if (m <= 8) { g = rf_gchunk<3>(P, cact + b, rb, V, lane); j = lane >> 3; }
-                else if (m <= 16) { g = rf_gchunk<4>(P, cact + b, rb, V, lane); j = lane >> 2; }
-                else { g = rf_gchunk<5>(P, cact + b, rb, V, lane); j = lane >> 1; }
-                if (j < m) {
-                    const double wo = cw[b + j], wn = wo * g;
-                    md = fmax(md, fabs(wn - wo));
-                    cw[b + j] = wn;           // the lanes that share j write the same bits
-                }
-            }
-            rf_wave_sync();
-            if (wave_max(md) < tol) break;
-        }
-        iters += it;
-        double S = 0.0;
-        for (int i = 0; i < cn; ++i) S += cw[i];
-        rf_wave_sync();
-        if (S > 0.0)
-            for (int i = lane; i < cn; i += 64) cw[i] = cw[i] / S;
-        rf_wave_sync();
-        double lp = 0.0, up = 0.0, sp = 0.0;
-        for (int v = lane; v < V; v += 64) {
-            double q = 0.0;
-            for (int i = 0; i < cn; ++i) q += cw[i] * P[cact[i] * V + v];
-            const uint32_t ni = hist[v];
-            if (ni != 0u) {
-                const double nv = (double)ni;
-                if (q > 0.0) {
-                    lp += nv * log(q);
-                    if (pass == 0) sp += (fb[v] / q) * P[trow * V + v];
-                } else up += nv;
-            }
-        }
+        r.iters += rf_fit(P, act, cw, n0 + pass, w.fb, counts, w.rb, V, lane, maxiter, tol);
+        const RfLoglik L = rf_loglik<true>(P, act, cw, n0 + pass, counts, w.fb, pass ? -1 : trow, V, lane);
         if (pass == 0) {
-            ll0 = wave_sum(lp); u0 = wave_sum(up); s = wave_sum(sp);
-            if (u0 == 0.0 && !(s > 1.0)) break;        // the null optimum is the optimum over A1 (KKT): the statistic is 0 exactly
+            f0 = L;
+            if (f0.u == 0.0 && !(f0.s > 1.0)) break;        // the null optimum is the optimum over A1 (KKT): the statistic is 0 exactly
         } else {
-            ll1 = wave_sum(lp); u1 = wave_sum(up); alt = true;
+            f1 = L; r.alt = true;
         }
     }
-    PrStat r;
-    r.s = s; r.alt = alt; r.iters = iters;
-    r.lam = !alt ? 0.0 : ((u0 > 0.0 && u1 < u0) ? __builtin_inf() : fmax(2.0 * (ll1 - ll0), 0.0));
+    r.s = f0.s;
+    r.lam = !r.alt ? 0.0 : ((f0.u > 0.0 && f1.u < f0.u) ? __builtin_inf() : fmax(2.0 * (f1.ll - f0.ll), 0.0));
     return r;
 }
 
@@ -189,9 +114,7 @@ __global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_obs(const PrArgs 
     const double* __restrict__ P = a.P;
     const int TD = a.T * a.D;
     for (;;) {
-        int j = 0;
-        if (lane == 0) j = atomicAdd(a.counter, 1);
-        j = __shfl(j, 0, 64);
+        const int j = rf_next_item(a.counter, lane);       // its contract shapes this loop: if / else, one closing fence
         if (j >= TD) break;
         const int d = j % a.D, t = a.targets[j / a.D];
         // ---- n_v (duplicate terms summed), N, f_v
@@ -219,32 +142,7 @@ __global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_obs(const PrArgs 
                 a.iters[j] = (unsigned long long)r.iters;
             }
         }
-        // every path ends here, the whole wave together: a `continue` after the lane-0 store above lets the compiler thread lane 0 straight into
-        // the lane-0 fetch of the next item, and the other 63 lanes then take their item from a lane that is not there
         rf_wave_sync();
-    }
-}
-
-// One wave draws the N draws of replicate b of item j into hist: simulate.hip's sim_draw_row (the same counter words, the same search over
-// the thresholds T_v - 1 of the terms v >= z, padded with 0xffffffff to the power of two P2), on an unsigned histogram.
-__device__ __forceinline__ void pr_draw(int lane, int P2, int z, uint32_t N, const uint32_t* thr, uint32_t* hist, uint32_t j, uint32_t b, uint32_t stream,
-                                        uint32_t k0, uint32_t k1)
-{
-    const uint32_t nblk = (N + 3u) >> 2;                       // N < 2^31
-    for (uint32_t i4 = (uint32_t)lane; i4 < nblk; i4 += 64u) {
-        uint32_t u[4];
-        int pos[4];
-        philox4x32_10(i4, j, kPrSimBit | b, stream, k0, k1, u);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) pos[k] = 0;
-        for (int step = P2 >> 1; step > 0; step >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (thr[pos[k] + step - 1] < u[k]) pos[k] += step;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (4u * i4 + (uint32_t)k < N) atomicAdd(&hist[z + pos[k]], 1u);
     }
 }
 
@@ -280,35 +178,17 @@ __global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_rep(const PrArgs 
         trow = tpos;
     }
     const double* __restrict__ P = P_LDS ? s_rows : a.P;
-    if (tid == 0) *s_z = 0;
-    __syncthreads();
-    // ---- p_v = sum_c w0_c P[c][v] (the zero weights outside A0 add nothing: same bits as the sum over all C), cum, S, thresholds: k_simulate's
+    __syncthreads();                                           // the staged rows are there
+    // ---- p_v = sum_c w0_c P[c][v] (the zero weights outside A0 add nothing: same bits as k_simulate's sum over all C), then its thresholds
     double* s_p = pr_carve(wave_base, a.Cp, V).fb;
-    double* s_cum = s_p + V;
     for (int v = tid; v < V; v += nt) {
         double p = 0.0;
         for (int i = 0; i < n0; ++i) p += w.w0[i] * P[w.act0[i] * V + v];
         s_p[v] = p;
     }
-    __syncthreads();
-    if (tid == 0) {
-        double c = 0.0;
-        for (int v = 0; v < V; ++v) { c += s_p[v]; s_cum[v] = c; }
-    }
-    __syncthreads();
-    const double S = s_cum[V - 1];
-    if (!(S > 0.0 && S <= 1.7976931348623157e308)) return;     // no status-0 item has such a null fit; without thresholds nothing may be drawn
-    const double two32 = 4294967296.0;
-    int nz = 0;
-    for (int v = tid; v < V; v += nt) nz += (unsigned long long)((s_cum[v] / S) * two32) == 0ull;
-    if (nz) atomicAdd(s_z, nz);
-    __syncthreads();
-    const int z = *s_z;                                        // T is non-decreasing and T_{V-1} = 2^32: the zeros lead, z <= V - 1
-    for (int v = tid; v < V; v += nt) {
-        const unsigned long long T = (unsigned long long)((s_cum[v] / S) * two32);       // floor: the product is exact and >= 0
-        if (v >= z) s_thr[v - z] = (uint32_t)(T - 1ull);
-    }
-    for (int k = V - z + tid; k < P2; k += nt) s_thr[k] = 0xffffffffu;
+    const DrawSetup su = draw_thresholds(tid, nt, V, P2, s_p, s_p + V, s_z, s_thr);
+    if (!su.ok) return;                                        // no status-0 item has such a null fit
+    const int z = su.z;
     __syncthreads();                                           // the running sums are read; wave 0's f and r take their place
     // ---- the wave's replicates
     const uint32_t N = (uint32_t)a.n_doc[d];
@@ -319,7 +199,7 @@ __global__ __launch_bounds__(64 * kPrMaxWaves) void k_presence_rep(const PrArgs 
     int ge = 0, zero = 0;
     unsigned long long its = 0ull;
     for (int b = bbeg + wave; b < bend; b += nw) {
-        pr_draw(lane, P2, z, N, s_thr, w.hist, (uint32_t)j, a.b0 + (uint32_t)b, a.stream, a.k0, a.k1);
+        draw_row(lane, P2, z, N, s_thr, w.hist, (uint32_t)j, a.b0 + (uint32_t)b, a.stream, a.k0, a.k1);
         rf_wave_sync();
         for (int v = lane; v < V; v += 64) w.fb[v] = (double)w.hist[v] / Nd;
         rf_wave_sync();
@@ -357,30 +237,11 @@ extern "C" int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_
     for (int i = 0; i < T; ++i) MMM_CHECK(ctx, targets[i] >= 0 && targets[i] < C, "mmm_presence_test: targets[%d] = %d is no row of the catalogue (C = %d)", i, targets[i], C);
     if (int rc = mmm_check_csr(ctx, "mmm_presence_test", D, V, doc_ptr, term, count)) return rc;
     std::vector<int32_t> n_doc((size_t)D);
-    for (int d = 0; d < D; ++d) {
-        uint64_t s = 0;
-        for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) {
-            s += (uint64_t)count[e];
-            if (s >= ((uint64_t)1 << 31))
-                return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_presence_test: document %d holds 2^31 or more counts (a draw's index is a 32-bit word: N_d < 2^31)", d);
-        }
-        n_doc[(size_t)d] = (int32_t)s;
-    }
-    // P[c][v] = cat[c][v] / sum_v cat[c][v], the sum in index order (mmm_refit_exposures' P)
-    std::vector<double> P((size_t)C * V);
-    for (int c = 0; c < C; ++c) {
-        double s = 0.0;
-        for (int v = 0; v < V; ++v) {
-            const double x = cat[(size_t)c * V + v];
-            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "mmm_presence_test: catalogue entry (%d, %d) is negative or not finite", c, v);
-            s += x;
-        }
-        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "mmm_presence_test: catalogue row %d sums to %g", c, s);
-        for (int v = 0; v < V; ++v) P[(size_t)c * V + v] = cat[(size_t)c * V + v] / s;
-    }
+    if (int rc = mmm_doc_totals(ctx, "mmm_presence_test", D, doc_ptr, count, n_doc.data())) return rc;
+    std::vector<double> P;           // the catalogue with rows normalised: mmm_refit_exposures' P
+    if (int rc = mmm_normalise_rows(ctx, "mmm_presence_test", C, V, cat, P)) return rc;
     if (D == 0) return MMM_OK;
     MMM_CHECK(ctx, w_null && stat && score && w_alt && count_ge && count_zero && status && iters, "mmm_presence_test: NULL output");
-    const int64_t nnz = doc_ptr[D];
     const size_t TD = (size_t)T * (size_t)D, TDC = TD * (size_t)C, DC = (size_t)D * C;
     const bool want_rep = rep_stat && B > 0;
 
@@ -388,17 +249,13 @@ extern "C" int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_
     const int wd = pr_wave_doubles(Cp, V);
     const size_t pw = sizeof(double) * (size_t)wd;
 
-    DevBuf<int64_t> dp; DevBuf<int32_t> tc, tg, nd, cnt, itm; DevBuf<double> Pd, outd, rep; DevBuf<uint8_t> alw; DevBuf<int8_t> st; DevBuf<unsigned long long> its;
+    DevCsr csr; DevBuf<int32_t> tg, nd, cnt, itm; DevBuf<double> Pd, outd, rep; DevBuf<uint8_t> alw; DevBuf<int8_t> st; DevBuf<unsigned long long> its;
     DevBuf<int> counter;
-    MMM_HIP(ctx, dp.alloc((size_t)D + 1)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, tg.alloc((size_t)T)); MMM_HIP(ctx, nd.alloc((size_t)D));
+    MMM_HIP(ctx, tg.alloc((size_t)T)); MMM_HIP(ctx, nd.alloc((size_t)D));
     MMM_HIP(ctx, Pd.alloc(P.size())); MMM_HIP(ctx, outd.alloc(TDC + 3 * TD)); MMM_HIP(ctx, st.alloc(TD)); MMM_HIP(ctx, its.alloc(TD));
     MMM_HIP(ctx, cnt.alloc(2 * TD)); MMM_HIP(ctx, counter.alloc(1));
     if (allowed) MMM_HIP(ctx, alw.alloc(DC));
-    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (int rc = csr.upload(ctx, D, doc_ptr, term, count)) return rc;
     MMM_HIP(ctx, hipMemcpyAsync(tg.p, targets, sizeof(int32_t) * (size_t)T, hipMemcpyHostToDevice, ctx->stream));
     MMM_HIP(ctx, hipMemcpyAsync(nd.p, n_doc.data(), sizeof(int32_t) * (size_t)D, hipMemcpyHostToDevice, ctx->stream));
     MMM_HIP(ctx, hipMemcpyAsync(Pd.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -412,7 +269,7 @@ extern "C" int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_
 
     PrArgs a{};
     a.D = D; a.C = C; a.V = V; a.Cp = Cp; a.T = T; a.maxiter = maxiter; a.tol = tol;
-    a.doc_ptr = dp.p; a.term = tc.p; a.count = tc.p + nnz; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.targets = tg.p;
+    a.doc_ptr = csr.ptr; a.term = csr.term; a.count = csr.count; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.targets = tg.p;
     a.w_null = outd.p; a.stat = outd.p + TDC; a.score = a.stat + TD; a.w_alt = a.score + TD; a.status = st.p; a.iters = its.p; a.counter = counter.p;
     a.n_doc = nd.p; a.B = B; a.b0 = (uint32_t)b0; a.k0 = (uint32_t)(seed & 0xffffffffull); a.k1 = (uint32_t)(seed >> 32); a.stream = stream;
     a.count_ge = cnt.p; a.count_zero = cnt.p + TD; a.wave_doubles = wd;

@@ -12,7 +12,7 @@
 // exchange in 64 and spill: 128 accumulator registers and 64 row offsets.
 #include "mmm_internal.h"
 #include "dev_math.h"
-#include "refit_reduce.cuh"
+#include "mixture_fit.cuh"
 
 namespace {
 
@@ -55,10 +55,9 @@ __global__ __launch_bounds__(64 * kRfMaxWaves) void k_refit(const RfArgs a)
     double* fb = nb + V;
     double* rb = fb + V;
 
+    const RfCountsF64 counts{nb};
     for (;;) {
-        int d = 0;
-        if (lane == 0) d = atomicAdd(a.counter, 1);
-        d = __shfl(d, 0, 64);
+        const int d = rf_next_item(a.counter, lane);       // its contract shapes this loop: if / else, one closing fence
         if (d >= a.D) break;
         // ---- n_v (duplicate terms summed: integer-valued doubles, exact in any order), N, f_v
         for (int v = lane; v < V; v += 64) rb[v] = 0.0;
@@ -76,118 +75,57 @@ __global__ __launch_bounds__(64 * kRfMaxWaves) void k_refit(const RfArgs a)
             fb[v] = N > 0.0 ? nv / N : 0.0;
         }
         // ---- A0
-        int n = 0;
-        for (int c0 = 0; c0 < C; c0 += 64) {
-            const int c = c0 + lane;
-            const bool on = c < C && (a.allowed ? a.allowed[(size_t)d * C + c] != 0 : true);
-            const unsigned long long m = __ballot(on);
-            if (on) actA[n + __popcll(m & ((1ull << lane) - 1ull))] = c;
-            n += __popcll(m);
-        }
-        rf_wave_sync();
+        int none;
+        int n = rf_active_list(a.allowed ? a.allowed + (size_t)d * C : nullptr, C, -1, actA, lane, none);
         if (N == 0.0 || n == 0) {
             if (lane == 0) a.unex[d] = N;       // everything else keeps the zeros (order: -1) the host has put there
-            continue;
-        }
-        for (int i = n + lane; i < ((n + 63) & ~63); i += 64) actA[i] = actA[0];
-        const double pen = a.penalty ? a.penalty[d] : 0.0;
-        double llA = 0.0, uA = 0.0;
-        long long iters = 0;
-        int round = 0, drop = 0;
-        bool first = true;
-        // candidate = the set whose fit runs next: A0 first, then A without its smallest weight
-        double* cw = wA; int* cact = actA; int cn = n;
-        for (;;) {
-            // ---- fit(candidate): cold start
-            const double w0 = 1.0 / (double)cn;
-            for (int i = lane; i < cn; i += 64) cw[i] = w0;
-            rf_wave_sync();
-            int it = 0;
-            while (it < a.maxiter) {
-                ++it;
-                // two of the lane's terms at a time: their sums over c are independent chains (each still in the order of c)
-                for (int v = lane; v < V; v += 128) {
-                    const bool two = v + 64 < V;
-                    const int v1 = two ? v + 64 : v;
-                    double q = 0.0, q1 = 0.0;
-#pragma unroll 4
-                    for (int i = 0; i < cn; ++i) {
-                        const double wi = cw[i];
-                        const int row = cact[i] * V;
-                        q += wi * P[row + v];
-                        q1 += wi * P[row + v1];
+        } else {
+            rf_pad_list(actA, n, lane);
+            const double pen = a.penalty ? a.penalty[d] : 0.0;
+            double llA = 0.0, uA = 0.0;
+            long long iters = 0;
+            int round = 0, drop = 0;
+            bool first = true;
+            // candidate = the set whose fit runs next: A0 first, then A without its smallest weight
+            double* cw = wA; int* cact = actA; int cn = n;
+            for (;;) {
+                iters += rf_fit(P, cact, cw, cn, fb, counts, rb, V, lane, a.maxiter, a.tol);
+                const RfLoglik B = rf_loglik<false>(P, cact, cw, cn, counts, fb, 0, V, lane);
+                // ---- decide
+                if (first) { first = false; llA = B.ll; uA = B.u; }
+                else {
+                    const double delta = B.u == uA ? llA - B.ll : __builtin_inf();
+                    if (!(delta < pen)) break;
+                    if (lane == 0) {
+                        if (a.order) a.order[(size_t)d * C + round] = actA[drop];
+                        if (a.cost) a.cost[(size_t)d * C + round] = delta;
                     }
-                    rb[v] = (nb[v] > 0.0 && q > 0.0) ? fb[v] / q : 0.0;
-                    if (two) rb[v1] = (nb[v1] > 0.0 && q1 > 0.0) ? fb[v1] / q1 : 0.0;
+                    ++round;
+                    double* tw = wA; wA = wB; wB = tw;
+                    int* ta = actA; actA = actB; actB = ta;
+                    llA = B.ll; n = cn;
                 }
-                rf_wave_sync();
-                double md = 0.0;
-                for (int b = 0; b < cn; b += 32) {
-                    const int m = min(32, cn - b);
-                    double g; int j;
-                    if (m <= 4) { g = rf_gchunk<2>(P, cact + b, rb, V, lane); j = lane >> 4; }
-                    else if (m <= 8) { g = rf_gchunk<3>(P, cact + b, rb, V, lane); j = lane >> 3; }
-                    else if (m <= 16) { g = rf_gchunk<4>(P, cact + b, rb, V, lane); j = lane >> 2; }
-                    else { g = rf_gchunk<5>(P, cact + b, rb, V, lane); j = lane >> 1; }
-                    if (j < m) {
-                        const double wo = cw[b + j], wn = wo * g;
-                        md = fmax(md, fabs(wn - wo));
-                        cw[b + j] = wn;           // the lanes that share j write the same bits
-                    }
-                }
-                rf_wave_sync();
-                if (wave_max(md) < a.tol) break;
-            }
-            iters += it;
-            double S = 0.0;
-            for (int i = 0; i < cn; ++i) S += cw[i];
-            rf_wave_sync();
-            if (S > 0.0)
-                for (int i = lane; i < cn; i += 64) cw[i] = cw[i] / S;
-            rf_wave_sync();
-            double lp = 0.0, up = 0.0;
-            for (int v = lane; v < V; v += 64) {
-                double q = 0.0;
-                for (int i = 0; i < cn; ++i) q += cw[i] * P[cact[i] * V + v];
-                const double nv = nb[v];
-                if (nv > 0.0) { if (q > 0.0) lp += nv * log(q); else up += nv; }
-            }
-            const double llB = wave_sum(lp), uB = wave_sum(up);
-            // ---- decide
-            if (first) { first = false; llA = llB; uA = uB; }
-            else {
-                const double delta = uB == uA ? llA - llB : __builtin_inf();
-                if (!(delta < pen)) break;
-                if (lane == 0) {
-                    if (a.order) a.order[(size_t)d * C + round] = actA[drop];
-                    if (a.cost) a.cost[(size_t)d * C + round] = delta;
-                }
-                ++round;
-                double* tw = wA; wA = wB; wB = tw;
-                int* ta = actA; actA = actB; actB = ta;
-                llA = llB; n = cn;
-            }
-            if (!a.penalty || n <= 1) break;
-            // ---- the member with the smallest weight, ties to the lowest c (the list is in the order of c)
-            double bv = __builtin_inf(); int bi = 0x7fffffff;
-            for (int i = lane; i < n; i += 64) { const double x = wA[i]; if (x < bv) { bv = x; bi = i; } }
+                if (!a.penalty || n <= 1) break;
+                // ---- the member with the smallest weight, ties to the lowest c (the list is in the order of c)
+                double bv = __builtin_inf(); int bi = 0x7fffffff;
+                for (int i = lane; i < n; i += 64) { const double x = wA[i]; if (x < bv) { bv = x; bi = i; } }
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ov = __shfl_xor(bv, off, 64); const int oi = __shfl_xor(bi, off, 64);
-                if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+                for (int off = 32; off > 0; off >>= 1) {
+                    const double ov = __shfl_xor(bv, off, 64); const int oi = __shfl_xor(bi, off, 64);
+                    if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+                }
+                drop = bi;
+                cn = n - 1;
+                rf_list_without(actA, actB, n, drop, lane);
+                rf_pad_list(actB, cn, lane);
+                cw = wB; cact = actB;
             }
-            drop = bi;
-            cn = n - 1;
-            for (int i = lane; i < cn; i += 64) actB[i] = actA[i < drop ? i : i + 1];
-            rf_wave_sync();
-            for (int i = cn + lane; i < ((cn + 63) & ~63); i += 64) actB[i] = actB[0];
-            cw = wB; cact = actB;
+            for (int i = lane; i < n; i += 64) {
+                a.w[(size_t)d * C + actA[i]] = wA[i];
+                a.active[(size_t)d * C + actA[i]] = 1;
+            }
+            if (lane == 0) { a.ll[d] = llA; a.unex[d] = uA; a.iters[d] = iters; }
         }
-        for (int i = lane; i < n; i += 64) {
-            a.w[(size_t)d * C + actA[i]] = wA[i];
-            a.active[(size_t)d * C + actA[i]] = 1;
-        }
-        if (lane == 0) { a.ll[d] = llA; a.unex[d] = uA; a.iters[d] = iters; }
         rf_wave_sync();
     }
 }
@@ -205,22 +143,11 @@ extern "C" int mmm_refit_exposures(mmm_ctx* ctx, int D, int C, int V, const int6
     MMM_CHECK(ctx, maxiter >= 1 && tol >= 0.0, "mmm_refit_exposures: maxiter = %d (>= 1), tol = %g (>= 0)", maxiter, tol);
     if ((size_t)C * (size_t)V >= ((size_t)1 << 31)) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_refit_exposures: C V = %zu (limit 2^31 - 1)", (size_t)C * V);
     if (int rc = mmm_check_csr(ctx, "mmm_refit_exposures", D, V, doc_ptr, term, count)) return rc;
-    // P[c][v] = cat[c][v] / sum_v cat[c][v], the sum in index order
-    std::vector<double> P((size_t)C * V);
-    for (int c = 0; c < C; ++c) {
-        double s = 0.0;
-        for (int v = 0; v < V; ++v) {
-            const double x = cat[(size_t)c * V + v];
-            MMM_CHECK(ctx, std::isfinite(x) && x >= 0.0, "mmm_refit_exposures: catalogue entry (%d, %d) is negative or not finite", c, v);
-            s += x;
-        }
-        MMM_CHECK(ctx, s > 0.0 && std::isfinite(s), "mmm_refit_exposures: catalogue row %d sums to %g", c, s);
-        for (int v = 0; v < V; ++v) P[(size_t)c * V + v] = cat[(size_t)c * V + v] / s;
-    }
+    std::vector<double> P;           // the catalogue with rows normalised
+    if (int rc = mmm_normalise_rows(ctx, "mmm_refit_exposures", C, V, cat, P)) return rc;
     if (penalty)
         for (int d = 0; d < D; ++d) MMM_CHECK(ctx, std::isfinite(penalty[d]) && penalty[d] >= 0.0, "mmm_refit_exposures: penalty[%d] is negative or not finite", d);
     if (D == 0) return MMM_OK;
-    const int64_t nnz = doc_ptr[D];
     const size_t DC = (size_t)D * C;
 
     // launch geometry: the catalogue in LDS when it fits, as many waves per block as the per-wave buffers leave room for
@@ -243,33 +170,30 @@ extern "C" int mmm_refit_exposures(mmm_ctx* ctx, int D, int C, int V, const int6
     const int64_t want = ((int64_t)D + nw - 1) / nw, resident = (int64_t)cus * per_cu;
     const unsigned grid = (unsigned)std::min(want, resident);
 
-    DevBuf<int64_t> dp; DevBuf<int32_t> tc, ord; DevBuf<double> Pd, pend, outd, ws; DevBuf<uint8_t> alw, act; DevBuf<int> counter;
-    MMM_HIP(ctx, dp.alloc((size_t)D + 1 + D)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, Pd.alloc(P.size()));
+    DevCsr csr; DevBuf<int32_t> ord; DevBuf<double> Pd, pend, outd, ws; DevBuf<uint8_t> alw, act; DevBuf<int> counter;
+    MMM_HIP(ctx, Pd.alloc(P.size()));
     MMM_HIP(ctx, outd.alloc(DC + (cost ? DC : 0) + 2 * (size_t)D)); MMM_HIP(ctx, act.alloc(DC)); MMM_HIP(ctx, counter.alloc(1));
     if (order) MMM_HIP(ctx, ord.alloc(DC));
     if (allowed) MMM_HIP(ctx, alw.alloc(DC));
     if (penalty) MMM_HIP(ctx, pend.alloc((size_t)D));
     if (!f_lds) MMM_HIP(ctx, ws.alloc((size_t)grid * nw * 3 * (size_t)V));
-    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (int rc = csr.upload(ctx, D, doc_ptr, term, count, (size_t)D)) return rc;       // the tail: iters
+    int64_t* const itd = csr.dp.p + D + 1;
     MMM_HIP(ctx, hipMemcpyAsync(Pd.p, P.data(), sizeof(double) * P.size(), hipMemcpyHostToDevice, ctx->stream));
     if (allowed) MMM_HIP(ctx, hipMemcpyAsync(alw.p, allowed, DC, hipMemcpyHostToDevice, ctx->stream));
     if (penalty) MMM_HIP(ctx, hipMemcpyAsync(pend.p, penalty, sizeof(double) * (size_t)D, hipMemcpyHostToDevice, ctx->stream));
     // what a document that never runs (N = 0, empty `allowed` row) and a round that never runs leave behind
     MMM_HIP(ctx, hipMemsetAsync(outd.p, 0, sizeof(double) * outd.n, ctx->stream));
-    MMM_HIP(ctx, hipMemsetAsync(dp.p + D + 1, 0, sizeof(int64_t) * (size_t)D, ctx->stream));
+    MMM_HIP(ctx, hipMemsetAsync(itd, 0, sizeof(int64_t) * (size_t)D, ctx->stream));
     MMM_HIP(ctx, hipMemsetAsync(act.p, 0, DC, ctx->stream));
     MMM_HIP(ctx, hipMemsetAsync(counter.p, 0, sizeof(int), ctx->stream));
     if (order) MMM_HIP(ctx, hipMemsetAsync(ord.p, 0xff, sizeof(int32_t) * DC, ctx->stream));
 
     RfArgs a;
     a.D = D; a.C = C; a.V = V; a.Cp = Cp; a.maxiter = maxiter; a.tol = tol;
-    a.doc_ptr = dp.p; a.term = tc.p; a.count = tc.p + nnz; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.penalty = penalty ? pend.p : nullptr;
+    a.doc_ptr = csr.ptr; a.term = csr.term; a.count = csr.count; a.P = Pd.p; a.allowed = allowed ? alw.p : nullptr; a.penalty = penalty ? pend.p : nullptr;
     a.w = outd.p; a.cost = cost ? outd.p + DC : nullptr; a.ll = outd.p + DC + (cost ? DC : 0); a.unex = a.ll + D;
-    a.active = act.p; a.order = order ? ord.p : nullptr; a.iters = (long long*)(dp.p + D + 1); a.counter = counter.p; a.ws = f_lds ? nullptr : ws.p;
+    a.active = act.p; a.order = order ? ord.p : nullptr; a.iters = (long long*)itd; a.counter = counter.p; a.ws = f_lds ? nullptr : ws.p;
     auto kern = p_lds ? k_refit<true, true> : (f_lds ? k_refit<false, true> : k_refit<false, false>);
     if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, ctx->stream, a);

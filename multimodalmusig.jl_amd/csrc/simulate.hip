@@ -13,7 +13,6 @@ constexpr int kSimWaves = 4;                 // waves per block; each takes one 
 constexpr int kSimThreads = 64 * kSimWaves;
 constexpr int kSimMaxV = 4096;               // LDS per block: pi 8 V + thresholds 4 p2(V) + kSimWaves histograms 16 V = 112 KiB at V = 4096 of 160 KiB;
                                              // a launch asks for ITS V (96 terms: 2.8 KiB)
-constexpr uint32_t kSimBit = 0x80000000u;    // high bit of the third counter word: free in the resampler and the split (b, rep < 2^31)
 
 // grid ceil(D / 4), one wave per document: S[d] = the sequential sum over v of p_v -- the S of the definition, for the host's check.  Lanes
 // form p of 64 terms at a time (phi coalesced), then every lane adds the 64 values in index order.
@@ -33,31 +32,6 @@ __global__ __launch_bounds__(kSimThreads) void k_sim_total(int D, int K, int V, 
         for (int j = 0; j < n; ++j) cum += __shfl(p, j, 64);
     }
     if (lane == 0) S[d] = cum;
-}
-
-// One wave draws the N draws of one (document, replicate) pair, 64 Philox blocks (256 draws) per step, into hist[0..V) with integer atomics.
-// thr[0..P): the thresholds T_v - 1 of the terms v >= z (z: the leading terms with T_v = 0, which no word reaches), padded with 0xffffffff to
-// the power of two P; the draw of the word u is z + the number of j with thr[j] < u = the first v with T_v > u.  thr[V - z - 1] = 2^32 - 1 is
-// never < u, so the result is <= V - 1.  The same log2(P) steps for every lane, no bound checks, a lane's four draws side by side.
-__device__ __forceinline__ void sim_draw_row(int lane, int P, int z, uint32_t N, const uint32_t* thr, int* hist, uint32_t d, uint32_t b, uint32_t stream,
-                                             uint32_t k0, uint32_t k1)
-{
-    const uint32_t nblk = (N + 3u) >> 2;                       // N < 2^31
-    for (uint32_t i4 = (uint32_t)lane; i4 < nblk; i4 += 64u) {
-        uint32_t u[4];
-        int pos[4];
-        philox4x32_10(i4, d, kSimBit | b, stream, k0, k1, u);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pos[j] = 0;
-        for (int step = P >> 1; step > 0; step >>= 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (thr[pos[j] + step - 1] < u[j]) pos[j] += step;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (4u * i4 + (uint32_t)j < N) atomicAdd(&hist[z + pos[j]], 1);
-    }
 }
 
 // the statistics of the count vector in hist (cleared on the way) against pi: the lane is the partial sum, wave_sum the butterfly
@@ -128,27 +102,10 @@ __global__ __launch_bounds__(kSimThreads) void k_simulate(int D, int K, int V, i
         for (int k = 0; k < K; ++k) p += pr[k] * phi[(size_t)k * V + v];
         s_pi[v] = p;
     }
-    __syncthreads();
-    if (tid == 0) {
-        double c = 0.0;
-        for (int v = 0; v < V; ++v) { c += s_pi[v]; s_cum[v] = c; }
-        s_z = 0;
-    }
-    __syncthreads();
-    const double S = s_cum[V - 1];
-    if (!(S > 0.0 && S <= 1.7976931348623157e308)) return;     // refused by the host; without thresholds nothing may be drawn
-    const double two32 = 4294967296.0;
-    int nz = 0;
-    for (int v = tid; v < V; v += kSimThreads) nz += (unsigned long long)((s_cum[v] / S) * two32) == 0ull;
-    if (nz) atomicAdd(&s_z, nz);
-    __syncthreads();
-    const int z = s_z;                                         // T is non-decreasing and T_{V-1} = 2^32: the zeros lead, z <= V - 1
-    for (int v = tid; v < V; v += kSimThreads) {
-        const unsigned long long T = (unsigned long long)((s_cum[v] / S) * two32);       // floor: the product is exact and >= 0
-        if (v >= z) s_thr[v - z] = (uint32_t)(T - 1ull);
-        s_pi[v] = s_pi[v] / S;
-    }
-    for (int j = V - z + tid; j < P; j += kSimThreads) s_thr[j] = 0xffffffffu;
+    const DrawSetup su = draw_thresholds(tid, kSimThreads, V, P, s_pi, s_cum, &s_z, s_thr);
+    if (!su.ok) return;                                        // refused by the host
+    const int z = su.z;
+    for (int v = tid; v < V; v += kSimThreads) s_pi[v] = s_pi[v] / su.S;
     __syncthreads();                                           // the running sums are read; the histograms take their place
     for (int v = lane; v < V; v += 64) s_hist[v] = 0;
     double pp = 0.0, cos_obs = 0.0, chi_obs = 0.0;
@@ -172,7 +129,7 @@ __global__ __launch_bounds__(kSimThreads) void k_simulate(int D, int K, int V, i
     int le = 0, ge = 0;
     for (int bb = bbeg; bb < bend; bb += kSimWaves) {          // block-uniform trip count: the barriers below are reached by every wave
         const int b = bb + wave;
-        if (b < bend) sim_draw_row(lane, P, z, N, s_thr, s_hist, d, b0 + (uint32_t)b, stream, k0, k1);
+        if (b < bend) draw_row(lane, P, z, N, s_thr, s_hist, d, b0 + (uint32_t)b, stream, k0, k1);
         __syncthreads();
         if (b < bend) {
             if (FIT) {
@@ -288,36 +245,23 @@ int mmm_fit_check(mmm_ctx* ctx, int D, int K, int V, const int64_t* doc_ptr, con
     if (int rc = mmm_check_csr(ctx, "mmm_fit_check", D, V, doc_ptr, term, count)) return rc;
     MMM_CHECK(ctx, D == 0 || (cos_obs && chi_obs && cos_le && chi_ge), "mmm_fit_check: NULL output");
     std::vector<int32_t> n_doc((size_t)D);
-    for (int d = 0; d < D; ++d) {
-        uint64_t s = 0;
-        for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) {
-            s += (uint64_t)count[e];
-            if (s >= ((uint64_t)1 << 31))
-                return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_fit_check: document %d holds 2^31 or more counts (a draw's index is a 32-bit word: N_d < 2^31)", d);
-        }
-        n_doc[(size_t)d] = (int32_t)s;
-    }
+    if (int rc = mmm_doc_totals(ctx, "mmm_fit_check", D, doc_ptr, count, n_doc.data())) return rc;
     SimTables t;
     if (int rc = sim_prepare(ctx, "mmm_fit_check", D, K, V, props, phi, n_doc.data(), B, b0, t)) return rc;
     if (D == 0) return MMM_OK;
     if (int rc = sim_set_lds<true>(ctx, t.lds)) return rc;
-    const int64_t nnz = doc_ptr[D];
     const size_t BD = (size_t)B * (size_t)D;
     const bool want_rep = (cos_rep || chi_rep) && BD;
-    DevBuf<int64_t> dp; DevBuf<int32_t> tc, cnt; DevBuf<double> obs, rep;
-    MMM_HIP(ctx, dp.alloc((size_t)D + 1)); MMM_HIP(ctx, tc.alloc(2 * (size_t)nnz)); MMM_HIP(ctx, cnt.alloc(2 * (size_t)D)); MMM_HIP(ctx, obs.alloc(2 * (size_t)D));
+    DevCsr csr; DevBuf<int32_t> cnt; DevBuf<double> obs, rep;
+    MMM_HIP(ctx, cnt.alloc(2 * (size_t)D)); MMM_HIP(ctx, obs.alloc(2 * (size_t)D));
     if (want_rep) MMM_HIP(ctx, rep.alloc(2 * BD));
-    MMM_HIP(ctx, hipMemcpyAsync(dp.p, doc_ptr, sizeof(int64_t) * ((size_t)D + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p, term, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        MMM_HIP(ctx, hipMemcpyAsync(tc.p + nnz, count, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (int rc = csr.upload(ctx, D, doc_ptr, term, count)) return rc;
     MMM_HIP(ctx, hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * 2 * (size_t)D, ctx->stream));
     MMM_HIP(ctx, hipMemsetAsync(obs.p, 0, sizeof(double) * 2 * (size_t)D, ctx->stream));
     if (want_rep) MMM_HIP(ctx, hipMemsetAsync(rep.p, 0, sizeof(double) * 2 * BD, ctx->stream));
     const int rpb = sim_reps_per_block(ctx, D, B);
     hipLaunchKernelGGL(k_simulate<true>, dim3((unsigned)D, (unsigned)std::max(1, (B + rpb - 1) / rpb)), dim3(kSimThreads), t.lds, ctx->stream, D, K, V, t.P, t.props.p,
-                       t.phi.p, t.n_doc.p, dp.p, tc.p, tc.p + nnz, B, (uint32_t)b0, rpb, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), stream,
+                       t.phi.p, t.n_doc.p, csr.ptr, csr.term, csr.count, B, (uint32_t)b0, rpb, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), stream,
                        (int32_t*)nullptr, obs.p, cnt.p, want_rep ? rep.p : (double*)nullptr);
     MMM_LAUNCH_CHECK(ctx);
     // staged on the host so that a failing copy leaves the caller's arrays as they were

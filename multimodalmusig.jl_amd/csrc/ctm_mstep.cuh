@@ -951,7 +951,7 @@ __global__ void k_ll_store(int M, const double* num, size_t num_stride, const do
 }
 
 // per-document ELBO pieces (MMCTM.jl:286-370): out[block][6] = {ElnPeta(without logdet/const), ElnPZ, ElnPX, ElnQeta, ElnQZ, count}
-// theta is rebuilt on the fly from (lam_prev, expE_prev) when theta == NULL
+// theta must be resident: the kernel reads it unconditionally, and elbo_enqueue (ctm.hip) runs materialise_theta for the selected replica first
 template <bool TAB_LDS>
 __global__ __launch_bounds__(kBlockS) void k_ctm_elbo_docs(CtmDev c, const double* invSigma, const double* mu, const double* lam, const double* nu,
                                                            const double* zeta, const double* theta, const double* Eeff, double* out)

@@ -227,6 +227,17 @@ int mmm_lda_prologue_moved(const mmm_lda* m);
 /* How the single-step E-step build forms a block's lambda statistics: 1 = as a block product B_kv sum_d a_dk r_dv (k_lda_estep_block), 0 = per-wave
  * LDS slabs (k_lda_estep: MMM_OFF_LDA_BLOCK_STATS, a corpus in which a document lists a term twice, or not the single-step build at all). */
 int mmm_lda_stats_build(const mmm_lda* m);
+/* Which launches the last training pass enqueued on this handle took (mmm_lda_iterate / mmm_lda_fit; 0 before the first), as MMM_PASS_* bits:
+ * MERGED = reduction, ll sweep and M-step in one launch, SPLIT = the reduce launch and k_lda_mstep, WIDE = the term sweep and
+ * k_lda_mstep_wide (BIG: its build for more than 32 topics); P2P = the ranks' exchange rode inside those launches (mailboxes), otherwise a
+ * communicating context all-reduced between them; LL_JOIN = the reduce blocks joined the ll sweep; PACKED = two logical reduce blocks per
+ * block; LL_CELLS = the ll blocks handed their sums to the reduce blocks through cells (exchange not folded). */
+enum { MMM_PASS_MERGED = 1, MMM_PASS_SPLIT = 2, MMM_PASS_WIDE = 4, MMM_PASS_P2P = 8, MMM_PASS_LL_JOIN = 16, MMM_PASS_PACKED = 32,
+       MMM_PASS_LL_CELLS = 64, MMM_PASS_BIG = 128 };
+int mmm_lda_last_pass(const mmm_lda* m);
+/* Blocks of that pass's launch that wait for each other -- the merged launch's reduce and ll blocks, or (LL_CELLS) the reduce launch's -- and so
+ * must be resident together; with the exchange folded in they also wait for the peers' blocks.  0 when no block of the pass waits for another. */
+int mmm_lda_last_pass_blocks(const mmm_lda* m);
 /* fit!(model; maxiter, tol) -- LDA.jl:198-224: iterate until |dll|/|ll| < tol after > 10 passes, then ELBO. */
 int mmm_lda_fit(mmm_lda* m, int maxiter, double tol, double* ll_hist, int* n_iter, int* converged,
                 double* elbo);

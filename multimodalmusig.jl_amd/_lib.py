@@ -79,6 +79,8 @@ _SIGS = {
     "mmm_lda_row_bytes": (C.c_int, [vp]),
     "mmm_lda_prologue_moved": (C.c_int, [vp]),
     "mmm_lda_stats_build": (C.c_int, [vp]),
+    "mmm_lda_last_pass": (C.c_int, [vp]),
+    "mmm_lda_last_pass_blocks": (C.c_int, [vp]),
     "mmm_lda_fit": (C.c_int, [vp, C.c_int, C.c_double, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "mmm_solver_opts_default": (None, [C.POINTER(SolverOpts)]),
     "mmm_lda_infer": (C.c_int, [vp, C.c_int, C.c_int, C.c_double, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -195,6 +197,9 @@ class TuningOpts(C.Structure):
 BUILDS = {"auto": 0, "sparse": 1, "dense": 2, "wide": 3}
 OFF = {"lda_padded_rows": 1 << 0, "lda_count_rows": 1 << 1, "lda_rows16": 1 << 2, "lda_ll_join": 1 << 3, "lda_merged": 1 << 4, "p2p_folded": 1 << 5,
        "ctm_packed": 1 << 6, "ctm_cpl": 1 << 7, "ctm_kfit": 1 << 8, "ctm_fused_gauss": 1 << 9, "ctm_ll_rows": 1 << 10, "lda_early_prologue": 1 << 11, "ctm_pipe_gauss": 1 << 12, "ctm_solve_order": 1 << 13, "lda_block_stats": 1 << 14, "refit_lds": 1 << 15, "decompose_lds": 1 << 16}
+
+
+PASS = {"merged": 1, "split": 2, "wide": 4, "p2p": 8, "ll_join": 16, "packed": 32, "ll_cells": 64, "big": 128}      # MMM_PASS_* (mmm_lda_last_pass)
 
 
 class Context:

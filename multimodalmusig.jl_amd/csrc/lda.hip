@@ -265,6 +265,8 @@ struct mmm_lda {
     DevBuf<double> aexp_next;           // single-step build: exp(Elntheta_{t+1}), D x K, written by the merged launch of pass t (its prologue blocks)
     int aexp_for = -1;                  // the pass whose Elntheta / aexp_next the last merged launch of THIS call has formed (prepare_call resets it)
     bool pro_used = false;              // some merged launch of this handle has run a next pass's prologue (mmm_lda_prologue_moved)
+    int pass_kind = 0;                  // launches of the last training pass enqueued (mmm_lda_last_pass: MMM_PASS_* bits)
+    int pass_blocks = 0;                // ... and the blocks of its launch that wait for each other (mmm_lda_last_pass_blocks; 0: none does)
     DevBuf<double> tabT;                // wide: [2][V][KP] term-major copies of the pass's exp(Elnbeta) and beta tables
     int stats_waves = 1;                // waves per term block of k_lda_stats_terms
     bool attr_big = false, attr_bigs = false;
@@ -727,6 +729,8 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
             MMM_LAUNCH_CHECK(ctx);
             m->aexp_for = ms.pro ? t + 1 : -1;
             if (ms.pro) m->pro_used = true;
+            m->pass_kind = MMM_PASS_MERGED | (r.p2p ? MMM_PASS_P2P : 0) | (ms.ll_join ? MMM_PASS_LL_JOIN : 0) | (epb == 2 ? MMM_PASS_PACKED : 0);
+            m->pass_blocks = ms.nredp + r.n_ll;      // (tests/sharded_ref.py merged_blocks restates nred, epb, n_ll and the cap: several ranks on one card must fit it together)
             if (do_ll) m->n_hist++;
             m->t = t;
             m->ll_pending = true;
@@ -763,6 +767,9 @@ int fused_passes(mmm_lda* m, int n_iter, double tol, int conv_base)
             hipLaunchKernelGGL(r.p2p ? k_lda_mstep<true> : k_lda_mstep<false>, dim3(m->K + 1), dim3(128), 0, ctx->stream, r, m->V, m->eta, m->ring(m->lambda),
                                m->ring(m->Elnbeta), m->ring(m->expElnbeta), m->ring(m->beta));
         MMM_LAUNCH_CHECK(ctx);
+        m->pass_kind = (m->wide ? MMM_PASS_WIDE | (m->KP > 32 ? MMM_PASS_BIG : 0) : MMM_PASS_SPLIT) | (r.p2p ? MMM_PASS_P2P : 0) |
+                       (via_cells && r.n_ll > 0 ? MMM_PASS_LL_CELLS : 0);
+        m->pass_blocks = (!m->wide && via_cells && r.n_ll > 0) ? nred + r.n_ll : 0;      // k_lda_reduce_ll's reduce blocks wait for its ll blocks' cells
         // host mirror, assuming no early stop (sync_ctl corrects it)
         if (do_ll) m->n_hist++;
         m->t = t;
@@ -1041,13 +1048,16 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     const int grid_max = std::max(m->grid_e, m->grid_s);
 #define A(buf, n) do { hipError_t e_ = m->buf.alloc(n); if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(" #buf "): %s", hipGetErrorString(e_)); return rc; } } while (0)
     A(doc_ptr, (size_t)D + 1); A(tc, (size_t)nnz);
-    for (int i = 0; i < 3; ++i) { A(lambda[i], Rs * VK); A(Elnbeta[i], Rs * VK); A(expElnbeta[i], Rs * VK); A(beta[i], Rs * VK); A(gamma[i], Rs * KD); A(Elntheta[i], Rs * KD); }
+    // (a rank may hold no document, D = 0: k_lda_estep_block and the merged launch's prologue read document 0's K values at a clamped index before
+    // they mask them -- the document rings and exp(Elntheta) keep room for one document)
+    const size_t KD1 = std::max(Rs * KD, (size_t)K);
+    for (int i = 0; i < 3; ++i) { A(lambda[i], Rs * VK); A(Elnbeta[i], Rs * VK); A(expElnbeta[i], Rs * VK); A(beta[i], Rs * VK); A(gamma[i], KD1); A(Elntheta[i], KD1); }
     A(theta, KD); A(phi, (size_t)K * nnz);
     const size_t VKp = (size_t)((V + 15) & ~15) * K;       // rows padded to 16 (k_lda_reduce_ll_mstep)
     A(partial, wide ? 1 : Rs * m->grid_e * VKp); A(stats[0], Rs * (VKp + 16)); A(stats[1], Rs * (VKp + 16)); A(scratch, VK + 16); A(llpart, Rs * grid_max);
     A(llpart2, Rs * 1024); A(elbopart, (size_t)m->grid_s * 5 + 8 * Rs);
     A(ctl, Rs); A(cells, 2 * 1024);
-    if (m->single_step && !ilda) A(aexp_next, KD);
+    if (m->single_step && !ilda) A(aexp_next, std::max(KD, (size_t)K));
     if (ilda) {
         A(fcells, (size_t)2 * 512 * 16);
         A(features, (size_t)I * V);
@@ -1422,6 +1432,10 @@ int mmm_lda_row_bytes(const mmm_lda* m)
 int mmm_lda_prologue_moved(const mmm_lda* m) { return (m && m->pro_used) ? 1 : 0; }
 
 int mmm_lda_stats_build(const mmm_lda* m) { return (m && m->block_stats) ? 1 : 0; }
+
+int mmm_lda_last_pass(const mmm_lda* m) { return m ? m->pass_kind : 0; }
+
+int mmm_lda_last_pass_blocks(const mmm_lda* m) { return m ? m->pass_blocks : 0; }
 
 int mmm_lda_ll_history(mmm_lda* m, double* ll, int max_n, int* n)
 {

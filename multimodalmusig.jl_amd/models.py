@@ -187,6 +187,16 @@ class LDA:
                 "row_bytes": int(lib().mmm_lda_row_bytes(self._h)), "prologue_moved": int(lib().mmm_lda_prologue_moved(self._h)),
                 "block_stats": int(lib().mmm_lda_stats_build(self._h))}
 
+    def last_pass(self):
+        """Names of the MMM_PASS_* bits of the last training pass enqueued (mmm_lda_last_pass): "merged" | "split" | "wide" (+ "big"), "p2p" when
+        the ranks' exchange rode inside those launches, "ll_join", "packed", "ll_cells"."""
+        bits = int(lib().mmm_lda_last_pass(self._h))
+        return {name for name, b in _lib.PASS.items() if bits & b}
+
+    def last_pass_blocks(self):
+        """Blocks of the last training pass's launch that wait for each other, 0 when none does (mmm_lda_last_pass_blocks)."""
+        return int(lib().mmm_lda_last_pass_blocks(self._h))
+
     def close(self):
         if self._h:
             lib().mmm_lda_destroy(self._h)

@@ -27,13 +27,10 @@
 #include "mmm_logtab.h"
 #include "mmm_exptab.h"
 #include "mmm_internal.h"
+#include "create_plan.h"
 
 namespace {
 
-constexpr int kMaxM = 8;
-constexpr int kKmax = 64;          // topics per modality (the theta loop is unrolled to 8 / 10 / 16 / 32; 33..64: the 64-topic build of the wide-table path;
-                                   // sum K > 64: ctm_big.cuh)
-constexpr int kWavesS = 4;         // stage / auxiliary kernels
 constexpr int kBlockS = kWavesS * MMM_WAVE;
 
 enum { F_ZETA = 1, F_THETA_COMPUTE = 2, F_THETA_STORED = 4, F_THETA_STORE = 8, F_NU = 16, F_LAMBDA = 32, F_SLAB = 64, F_ORDER_LAM = 128 };
@@ -59,24 +56,22 @@ struct SolveOpts { double xtol_rel, xtol_abs, nu_lower; int xtol_rule, max_eval;
 
 #include "ctm_mstep.cuh"
 
+static_assert(kPlanWave == MMM_WAVE && kCtmBigSlots == kBigSlots && sizeof(CountPair) == sizeof(int2), "create_plan.h / corpus_forms.h restate these");
+
 } // namespace
 
 // =====================================================================================================================
 // A handle holds R >= 1 independent models ("replicas": the restarts of scripts/run_mmctm.jl:77-134) over ONE resident
 // corpus.  Every per-model array is R contiguous copies; batched launches put the replica on grid.y.  The classic
 // single-model API works on the selected replica (`sel`, 0 by default).
-struct mmm_ctm {
+struct mmm_ctm : CtmPlan {      // the plan the handle was created with (create_plan.h): builds and launch geometry
     mmm_ctx* ctx = nullptr;
     mmm_tuning_opts tune{};        // the caller's choices at create time (mmm_ctx_set_tuning)
     CtmDims dm{};
     CtmTopics tp{};
     bool immctm = false;
     int R = 1, sel = 0;
-    int L = 64, GM = 0 /* model-layout gamma size */;
-    int Ls = 64;                   // lanes per document in the solve phase: L, or sum K for the packed builds (6 / 12), or 2 / 4 (cpl > 1)
-    int cpl = 1;                   // coordinates per lane in the solve phase (k_ctm_solve_cpl: sum K = 10, 14, 28)
-    int lam_occ = 4;               // waves per SIMD of the persistent solve build (3 for sum K = 28)
-    bool persist = false;          // solve phase by k_ctm_solve_cpl (persistent waves, document slots refilled): cpl > 1, or cpl = 1 with Ls = L
+    int GM = 0 /* model-layout gamma size */;
     int64_t nnz = 0, theta_n = 0;
     long long nnzm[kMaxM] = {0};
     double Dglobal = 0;
@@ -89,10 +84,7 @@ struct mmm_ctm {
     DevBuf<int> nev_nu, nev_lam, status, active, npass;
     DevBuf<int> doclist;                       // the document list of the last mmm_ctm_update_docs call (grown on demand)
     std::vector<int64_t> h_doc_ptr;            // host copy of doc_ptr: the per-document spans of theta (mmm_ctm_get_doc / set_doc)
-    // dense corpora: the fused pass's theta phase over rows of 16-bit counts, one launch per modality (k_ctm_theta_dense)
-    bool tdense = false; int tSL[kMaxM] = {0};
-    DevBuf<unsigned short> trows[kMaxM];      // [D][16][SL_m rounded up to even]: lane-major rows of counts (a lane's part of a row is one load)
-    bool big = false;              // 64 < sum K <= 256: the generic kernels of ctm_big.cuh (one wave per document, several coordinates per lane)
+    DevBuf<unsigned short> trows[kMaxM];      // tdense: [D][16][SL_m rounded up to even]: lane-major rows of counts (a lane's part of a row is one load)
     DevBuf<double> big_scratch;    // [R][2 MK^2]: Sigma and its inverse during the Gaussian M-step / the ELBO's logdet
     int stop_enable = 0; double stop_tol = 0.0;     // set by fit_scope around a pass: the ll kernels apply the stopping rule
     int* pin_flags = nullptr;                       // pinned [2][2R]: snapshots of (active | status) the host reads one pass late
@@ -104,9 +96,7 @@ struct mmm_ctm {
     std::vector<std::unique_ptr<DevBuf<double>>> theta_spill;
     int theta_rep = -1;                       // replica whose theta is in the theta buffer (-1: none)
     int cap_hist = 0;
-    int grid_e = 1, waves_e = 8, grid_s = 1, grid_m = 1, grid_v = 1, waves_s = 4;
-    // wide tables (sum_m K_m V_m beyond LDS): theta phase without table / slabs in LDS + k_ctm_stats_terms over posting lists
-    bool wide = false;
+    // wide: k_ctm_stats_terms over posting lists
     int stats_waves = 1, nterms = 0;
     DevBuf<int64_t> term_ptr;      // [sum V + 1], modality-major
     DevBuf<int2> tpost;            // (document, count) per posting
@@ -167,22 +157,6 @@ int launch_estep_L(mmm_ctm* m, const CtmEArgs& a, size_t lds, int grid, int wave
     return launch_k<DL>(m->ctx, estep_kernel<DL, L, PH, MKT, KMX, OCC, WIDE, PACK>(), dim3(grid, nrep), dim3(waves * MMM_WAVE), lds, a, dl);
 }
 
-size_t estep_lds(const mmm_ctm* m, int flags)     // theta phase
-{
-    const int G = MMM_WAVE / m->L;
-    if (m->wide) return sizeof(double) * (size_t)m->waves_e * G * 2 * m->L;
-    size_t n = (size_t)m->dm.GT + (size_t)m->waves_e * G * ((flags & F_SLAB) ? 1 : 2) * m->L;      // (the fused pass: one scratch row per group)
-    int slabn = 0;      // a wave's slab holds one modality at a time
-    for (int i = 0; i < m->dm.M; ++i) slabn = std::max(slabn, m->dm.K[i] * m->dm.V[i]);
-    if (flags & F_SLAB) n += (size_t)m->waves_e * slabn;
-    return n * sizeof(double);
-}
-
-// shard sizes (documents, on a 256-CU device) below which the solve phase takes more lanes per document (create_impl; measured: profiles/r05_solve_layouts.jsonl)
-constexpr int kSolve10Lanes8Below = 75000;      // sum K = 10: 2 lanes x 5 coordinates -> 8 lanes x 2
-constexpr int kSolve28Lanes32Below = 9000;        // sum K = 28: 16 lanes x 2 coordinates -> 32 lanes x 1
-constexpr int kSolve28Waves4From = 40000;         // sum K = 28 as 16 x 2: three -> four persistent waves per SIMD
-
 // LDS of the Gaussian M-step block: the augmented matrix twice (block_inverse_pipelined, sum K <= 32) or A and its inverse (block_inverse_wide)
 inline size_t gauss_lds_doubles(int MK) { return (size_t)(MK <= 32 ? 4 : 2) * MK * MK; }
 
@@ -196,21 +170,13 @@ size_t solve_lds(const mmm_ctm* m)
     return sizeof(double) * ((size_t)m->dm.MK * m->dm.MK + m->dm.MK + (size_t)m->waves_s * scrw);
 }
 
-size_t theta_dense_lds(const mmm_ctm* m, int i, int kmx)
-{
-    const int NW = m->waves_e;
-    return sizeof(double) * ((size_t)16 * m->tSL[i] * kmx + (size_t)NW * 16 * m->tSL[i] * kmx + (size_t)NW * 4 * kmx + (size_t)NW * MMM_WAVE * kmx);
-}
-
-inline int theta_dense_kmx(int Km) { return Km <= 8 ? 8 : (Km <= 10 ? 10 : 16); }
-
 // the theta phase of the fused pass over rows of counts: one launch per modality (k_ctm_theta_dense)
 int launch_theta_dense(mmm_ctm* m, const CtmEArgs& a, int nrep)
 {
     mmm_ctx* ctx = m->ctx;
     for (int i = 0; i < m->dm.M; ++i) {
         const int kmx = theta_dense_kmx(m->dm.K[i]);
-        const size_t lds = theta_dense_lds(m, i, kmx);
+        const size_t lds = ctm_theta_dense_lds(*m, i, kmx);
         auto go = [&](auto kern) -> int {
             if (lds > 48 * 1024) MMM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(kern, dim3(m->grid_e, nrep), dim3(m->waves_e * MMM_WAVE), lds, ctx->stream, a, i, (const unsigned short*)m->trows[i].p);
@@ -344,7 +310,7 @@ int run_estep(mmm_ctm* m, Scope sc, int flags, const double* lam_in, double* lam
     CtmEArgs a = estep_args(m, sc, flags, lam_in, lam_out, expE, lam_keep, expE_keep);
     int rc;
     if (flags & (F_ZETA | F_THETA_COMPUTE | F_THETA_STORED | F_SLAB)) {
-        const size_t lds = estep_lds(m, flags);
+        const size_t lds = ctm_estep_lds(*m, m->dm.M, m->dm.K, m->dm.V, (flags & F_SLAB) != 0);
         if (lds > 160 * 1024) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "CTM theta phase needs %zu B of LDS (> 160 KiB)", lds);
         ProfSpan span(m->ctx, 1);   // mmm_ctx_profile_select(1): theta phase
         if (m->tdense && (flags & F_SLAB) && (flags & F_THETA_COMPUTE) && !(flags & (F_THETA_STORE | F_THETA_STORED))) {
@@ -370,7 +336,7 @@ int run_estep_docs(mmm_ctm* m, int flags, const double* expE, const int* docs_de
     const DocList dl{docs_dev, n};
     int rc;
     if (flags & (F_ZETA | F_THETA_COMPUTE | F_THETA_STORED)) {
-        const size_t lds = estep_lds(m, flags);
+        const size_t lds = ctm_estep_lds(*m, m->dm.M, m->dm.K, m->dm.V, (flags & F_SLAB) != 0);
         if (lds > 160 * 1024) return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "CTM theta phase needs %zu B of LDS (> 160 KiB)", lds);
         const int per_block = m->waves_e * (MMM_WAVE / m->L);
         if ((rc = launch_phase<0, true>(m, a, lds, std::min(m->grid_e, (n + per_block - 1) / per_block), m->waves_e, 1, dl))) return rc;
@@ -722,213 +688,104 @@ int upload_active(mmm_ctm* m)
     return MMM_OK;
 }
 
-int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, const double* alpha, const int64_t* doc_ptr, const int32_t* term,
-                const int32_t* count, const int* n_feat, const int* J, const int32_t* features, const double* gamma0,
-                const mmm_solver_opts* opts, mmm_ctm** out)
+// create, step 1b: the caller's corpus -- M CSR segments of D + 1 offsets, each continuing the one before -- checked and packed in one
+// sweep: tc = (term, count) pairs, Ndm[d][i] = document d's counts in modality i, hNm[i] = modality i's counts
+int check_corpus(mmm_ctx* ctx, int D, int M, const int* V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count,
+                 std::vector<CountPair>& tc, std::vector<double>& Ndm, std::vector<double>& hNm)
 {
-    if (!ctx) return MMM_ERR_ARG;
-    MMM_CHECK(ctx, out && K && V && alpha && doc_ptr && gamma0, "mmm_ctm_create: NULL argument");
-    MMM_CHECK(ctx, D >= 0 && M >= 1 && M <= kMaxM && R >= 1, "mmm_ctm_create: bad sizes D=%d M=%d (M <= %d) R=%d", D, M, kMaxM, R);
-    *out = nullptr;
-    MMM_HIP(ctx, hipSetDevice(ctx->device));
-    mmm_ctm* m = new mmm_ctm();
-    m->ctx = ctx; m->R = R;
-    CtmDims& dm = m->dm;
-    dm.D = D; dm.M = M; dm.koff[0] = 0; dm.goff[0] = 0;
-    int64_t toff = 0;
-    for (int i = 0; i < M; ++i) {
-        if (K[i] < 1 || K[i] > kKmax || V[i] < 1) { int rc = mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ctm_create: K[%d]=%d must be in 1..%d and V[%d]=%d >= 1", i, K[i], kKmax, i, V[i]); delete m; return rc; }
-        dm.K[i] = K[i]; dm.V[i] = V[i];
-        dm.koff[i + 1] = dm.koff[i] + K[i]; dm.goff[i + 1] = dm.goff[i] + K[i] * V[i];
-        dm.estart[i] = doc_ptr[(size_t)i * (D + 1)];
-        dm.toff[i] = toff;
-        m->nnzm[i] = doc_ptr[(size_t)i * (D + 1) + D] - dm.estart[i];
-        toff += m->nnzm[i] * K[i];
-    }
-    dm.MK = dm.koff[M]; dm.GT = dm.goff[M];
-    if (dm.MK > 64 * kBigSlots) { int rc = mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ctm_create: sum(K)=%d must be <= %d", dm.MK, 64 * kBigSlots); delete m; return rc; }
-    m->L = dm.MK <= 16 ? 16 : (dm.MK <= 32 ? 32 : 64);
-    m->big = dm.MK > 64;      // more coordinates than lanes: the generic kernels of ctm_big.cuh (and the wide-table data flow)
-    const int64_t nnz = doc_ptr[(size_t)(M - 1) * (D + 1) + D];
-    m->nnz = nnz; m->theta_n = toff;
-    m->h_doc_ptr.assign(doc_ptr, doc_ptr + (size_t)M * (D + 1));
-    // validate + pack the corpus
-    std::vector<int2> tc((size_t)nnz);
-    std::vector<double> Ndm((size_t)D * M, 0.0);
-    m->hNm.assign(M, 0.0);
-    if (doc_ptr[0] != 0) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: doc_ptr[0] != 0"); delete m; return rc; }
+    // (filled as locals and handed over at the end: the compiler knows that a vector it has just allocated overlaps neither term nor count,
+    // and keeps the sweep's loads out of the way of its stores -- through the references the sweep took 1 ms longer at 7.6 M entries)
+    std::vector<CountPair> pairs((size_t)doc_ptr[(size_t)(M - 1) * (D + 1) + D]);
+    std::vector<double> ndm((size_t)D * M, 0.0), nm((size_t)M, 0.0);
+    MMM_CHECK(ctx, doc_ptr[0] == 0, "mmm_ctm_create: doc_ptr[0] != 0");
     for (int i = 0; i < M; ++i) {
         const int64_t* dp = doc_ptr + (size_t)i * (D + 1);
-        if (i > 0 && dp[0] != doc_ptr[(size_t)(i - 1) * (D + 1) + D]) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: doc_ptr of modality %d does not continue modality %d", i, i - 1); delete m; return rc; }
+        MMM_CHECK(ctx, i == 0 || dp[0] == doc_ptr[(size_t)(i - 1) * (D + 1) + D], "mmm_ctm_create: doc_ptr of modality %d does not continue modality %d", i, i - 1);
         for (int d = 0; d < D; ++d) {
-            if (dp[d + 1] < dp[d]) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: doc_ptr not monotone (m=%d d=%d)", i, d); delete m; return rc; }
+            MMM_CHECK(ctx, dp[d + 1] >= dp[d], "mmm_ctm_create: doc_ptr not monotone (m=%d d=%d)", i, d);
             double n = 0.0;
             for (int64_t e = dp[d]; e < dp[d + 1]; ++e) {
-                if (term[e] < 0 || term[e] >= V[i] || count[e] < 0) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: entry %lld out of range", (long long)e); delete m; return rc; }
-                tc[(size_t)e] = make_int2(term[e], count[e]);
+                MMM_CHECK(ctx, term[e] >= 0 && term[e] < V[i] && count[e] >= 0, "mmm_ctm_create: entry %lld out of range", (long long)e);
+                pairs[(size_t)e] = CountPair{term[e], count[e]};
                 n += count[e];
             }
-            Ndm[(size_t)d * M + i] = n;
-            if (n > 0) m->hNm[i] += n;        // MMCTM.jl:409-414: only documents with N > 0 enter the ll
+            ndm[(size_t)d * M + i] = n;
+            if (n > 0) nm[(size_t)i] += n;        // MMCTM.jl:409-414: only documents with N > 0 enter the ll
         }
     }
-    // topics descriptor
+    tc.swap(pairs); Ndm.swap(ndm); hNm.swap(nm);
+    return MMM_OK;
+}
+
+// create, between plan and upload: the topics descriptor (MMCTM: gamma as the [m][k][v] tables; IMMCTM: [m][k][i][j] from n_feat, J and
+// features, which are checked here), and with it the sizes of alpha and of the model-layout gamma.  n_features: entries of `features`
+int topics_descriptor(mmm_ctm* m, const int* n_feat, const int* J, const int32_t* features, size_t* n_features)
+{
+    mmm_ctx* ctx = m->ctx;
+    const CtmDims& dm = m->dm;
+    const int M = dm.M;
     CtmTopics& tp = m->tp;
     m->immctm = (n_feat != nullptr);
     tp.immctm = m->immctm ? 1 : 0;
-    int nalpha = M, GM = dm.GT;
-    std::vector<int> featv;
-    if (m->immctm) {
-        if (!J || !features) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: IMMCTM needs J and features"); delete m; return rc; }
-        tp.aoff[0] = 0; tp.mgoff[0] = 0;
-        long long fo = 0;
-        for (int i = 0; i < M; ++i) {
-            tp.nfeat[i] = n_feat[i];
-            tp.aoff[i + 1] = tp.aoff[i] + n_feat[i];
-            if (tp.aoff[i + 1] > 4 * kMaxM) { int rc = mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ctm_create: more than %d features in total", 4 * kMaxM); delete m; return rc; }
-            int sj = 0;
-            for (int q = 0; q < n_feat[i]; ++q) { tp.J[tp.aoff[i] + q] = J[tp.aoff[i] + q]; sj += J[tp.aoff[i] + q]; }
-            tp.SJ[i] = sj;
-            tp.mgoff[i + 1] = tp.mgoff[i] + K[i] * sj;
-            tp.foff[i] = fo;
-            for (int q = 0; q < n_feat[i]; ++q) for (int v = 0; v < V[i]; ++v) {
-                const int f = features[fo + (long long)q * V[i] + v];
-                if (f < 0 || f >= J[tp.aoff[i] + q]) { int rc = mmm_fail(ctx, MMM_ERR_ARG, "mmm_ctm_create: feature value out of range"); delete m; return rc; }
-            }
-            fo += (long long)n_feat[i] * V[i];
-        }
-        featv.assign(features, features + fo);
-        nalpha = tp.aoff[M]; GM = tp.mgoff[M];
-    } else {
+    m->nalpha = M; m->GM = dm.GT; *n_features = 0;
+    if (!m->immctm) {
         for (int i = 0; i <= M; ++i) tp.mgoff[i] = dm.goff[i];
+        return MMM_OK;
     }
-    m->GM = GM;
-    m->tune = ctx->tune;
-    mmm_solver_opts so; mmm_solver_opts_default(&so);
-    if (opts) so = *opts;
-    m->opt = SolveOpts{so.xtol_rel, so.xtol_abs, so.nu_lower, so.xtol_rule, so.max_eval > 0 ? so.max_eval : 2000};
-    // launch geometry
-    const int G = MMM_WAVE / m->L;
-    m->waves_e = 8;
-    while (m->waves_e > 1 && estep_lds(m, F_SLAB) > 150 * 1024) m->waves_e >>= 1;
-    // table + one slab beyond LDS: the wide path (theta phase through L2, gamma statistics by k_ctm_stats_terms).  ctm_build =
-    // MMM_BUILD_WIDE forces it for any shape (tests, A/B)
-    int kmax_all = 0;
-    for (int i = 0; i < dm.M; ++i) kmax_all = std::max(kmax_all, dm.K[i]);
-    if (estep_lds(m, F_SLAB) > 160 * 1024 || ctx->tune.ctm_build == MMM_BUILD_WIDE || kmax_all > 32 || m->big) { m->wide = true; m->waves_e = 8; }
-    const int dpb = m->waves_e * G;
-    const int per_cu = m->wide ? 2 : std::max(1, (int)((160 * 1024) / estep_lds(m, F_SLAB)));
-    const int ncu = mmm_geo_cus(ctx);      // the CU count the geometry (and so the association of the cross-document sums) is derived from
-    m->grid_e = std::max(1, std::min((D + dpb - 1) / dpb, ncu * std::min(per_cu, 2)));
-    // Dense corpora: the fused pass's theta phase over rows of 16-bit counts (k_ctm_theta_dense), when every modality has at most 16 topics
-    // and 128 terms, no document lists a term twice, every count fits 16 bits and at least half of the D x V_m entries are present.
-    // ctm_build = MMM_BUILD_DENSE / _SPARSE forces / forbids it (tests, A/B); by default corpora of at least 32 documents per CU take it (below, a block of
-    // the 16-lane layout has less than one wave step and the slab kernel is as fast).
-    {
-        const int dmode = ctx->tune.ctm_build == MMM_BUILD_DENSE ? 1 : (ctx->tune.ctm_build == MMM_BUILD_AUTO ? -1 : 0);
-        bool ok = !m->wide && !m->big && dmode != 0 && D > 0 && (int64_t)D * dm.MK * 8 < ((int64_t)1 << 32) && D < (1 << 24);      // (32-bit byte offsets into lambda and into the rows)
-        int64_t present = 0, cells = 0;
-        for (int i = 0; i < M && ok; ++i) {
-            const int sl = dm.V[i] <= 32 ? 2 : (dm.V[i] <= 48 ? 3 : (dm.V[i] <= 96 ? 6 : (dm.V[i] <= 128 ? 8 : 0)));
-            if (sl == 0 || dm.K[i] > 16 || theta_dense_kmx(dm.K[i]) * sl > 64) { ok = false; break; }      // (the statistics must stay in registers)
-            m->tSL[i] = sl;
-            present += m->nnzm[i]; cells += (int64_t)D * dm.V[i];
+    MMM_CHECK(ctx, J && features, "mmm_ctm_create: IMMCTM needs J and features");
+    tp.aoff[0] = 0; tp.mgoff[0] = 0;
+    long long fo = 0;
+    for (int i = 0; i < M; ++i) {
+        tp.nfeat[i] = n_feat[i];
+        tp.aoff[i + 1] = tp.aoff[i] + n_feat[i];
+        if (tp.aoff[i + 1] > 4 * kMaxM) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ctm_create: more than %d features in total", 4 * kMaxM);
+        int sj = 0;
+        for (int q = 0; q < n_feat[i]; ++q) { tp.J[tp.aoff[i] + q] = J[tp.aoff[i] + q]; sj += J[tp.aoff[i] + q]; }
+        tp.SJ[i] = sj;
+        tp.mgoff[i + 1] = tp.mgoff[i] + dm.K[i] * sj;
+        tp.foff[i] = fo;
+        for (int q = 0; q < n_feat[i]; ++q) for (int v = 0; v < dm.V[i]; ++v) {
+            const int f = features[fo + (long long)q * dm.V[i] + v];
+            MMM_CHECK(ctx, f >= 0 && f < J[tp.aoff[i] + q], "mmm_ctm_create: feature value out of range");
         }
-        if (ok && 2 * present < cells) ok = false;
-        if (ok && dmode < 0 && D < 32 * ncu) ok = false;
-        std::vector<std::vector<unsigned short>> rows((size_t)M);
-        for (int i = 0; i < M && ok; ++i) {
-            const int sls = (m->tSL[i] + 1) & ~1, Vp = 16 * sls;     // lane-major: the slots of lane l (terms l, 16 + l, ...) are contiguous, an even number
-            rows[i].assign((size_t)D * Vp + 8, 0);      // (+ 16 bytes: k_ctm_loglik_dense reads 16 bytes from a lane's first slot)
-            std::vector<int> seen((size_t)dm.V[i], -1);
-            const int64_t* dp = doc_ptr + (size_t)i * (D + 1);
-            for (int d = 0; d < D && ok; ++d)
-                for (int64_t e = dp[d]; e < dp[d + 1]; ++e) {
-                    if (seen[(size_t)term[e]] == d || count[e] >= 65536) { ok = false; break; }
-                    seen[(size_t)term[e]] = d;
-                    rows[i][(size_t)d * Vp + (term[e] & 15) * sls + (term[e] >> 4)] = (unsigned short)count[e];
-                }
-        }
-        if (ok) {
-            m->waves_e = 8;
-            for (int i = 0; i < M; ++i) if (theta_dense_lds(m, i, theta_dense_kmx(dm.K[i])) > 160 * 1024) ok = false;
-        }
-        if (ok) {
-            m->tdense = true;
-            m->grid_e = std::max(1, std::min((D + 31) / 32, ncu));
-            for (int i = 0; i < M; ++i) {
-                hipError_t e_ = m->trows[i].alloc(rows[i].size());
-                if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(trows): %s", hipGetErrorString(e_)); delete m; return rc; }
-                if (hipMemcpy(m->trows[i].p, rows[i].data(), sizeof(unsigned short) * rows[i].size(), hipMemcpyHostToDevice) != hipSuccess) {
-                    int rc = mmm_fail(ctx, MMM_ERR_HIP, "upload of the rows of counts failed"); delete m; return rc;
-                }
-            }
-        }
+        fo += (long long)n_feat[i] * dm.V[i];
     }
-    if (ctx->tune.grid_blocks > 0) m->grid_e = ctx->tune.grid_blocks;
-    // (one block short of four per CU: the log-likelihood launch carries the Gaussian M-step as one block more, and a 1,025th block waits for a
-    // slot -- a second round of one block: + 3.3 us at config 5, + 4.6 us at config 4)
-    m->grid_s = std::max(1, std::min((D + kWavesS - 1) / kWavesS, ncu * 4 - 1));
-    m->waves_s = 4;
-    // solve phase: packed document groups (sum K lanes per document) for the shapes with a build (MMM_OFF_CTM_PACKED: the 16-lane rows)
-    m->Ls = m->L;
-    {
-        if (!mmm_off(ctx->tune, MMM_OFF_CTM_PACKED) && (dm.MK == 6 || dm.MK == 10 || dm.MK == 12)) m->Ls = dm.MK;
-        // several coordinates per lane (k_ctm_solve_cpl): sum K = 10 -> 2 lanes x 5 coordinates (32 document slots per wave; BASELINE config 5:
-        // solve phase 334 -> 263 us); sum K = 28 -> 16 lanes, 14 of them x 2 coordinates (round 3; 4 slots per wave, 134 VGPRs at 3 waves per
-        // SIMD, no scratch: BASELINE config 4 solve phase 1,096 -> 974 us at pass 20, 794 -> 757 us at pass 60 -- and the sums of a document
-        // are associated exactly as the 32-lane butterfly associates them, so not a bit changes).  MMM_OFF_CTM_CPL switches the path off
-        // (one coordinate per lane, lock step: k_ctm_estep<L, 1>).
-        const int want = ctx->tune.solve_lanes;      // 0: by shape and corpus size
-        const bool lockstep10 = dm.MK == 10 && want == 16;      // sum K = 10 with solve_lanes = 16: the packed / 16-lane lock-step build (A/B)
-        if (!mmm_off(ctx->tune, MMM_OFF_CTM_CPL) && !lockstep10) {
-            // Which layout: the full-size configurations keep the layouts of rounds 2-3 (most documents per wave trip); a SHARD -- D small
-            // enough that those layouts leave SIMDs without a wave or slots without a document -- takes more lanes per document
-            // (profiles/r05_shard_sizes.jsonl: sum K = 10 at 12,505 documents 2 x 5 -> 8 x 2; sum K = 28 at 6,249 documents 16 x 2 -> 32 x 1).
-            if (dm.MK == 10) {
-                // The two sum K = 10 layouts associate a document's sums differently, so this choice decides bits: it is made from D alone, and
-                // a restart batch takes what a single handle on the same corpus takes (replica r is bitwise the single fit of its gamma0).  The
-                // sum K = 28 choices below change no bit (both layouts associate as the 32-lane butterfly does; the wave count only deals the
-                // documents out) and count the replicas that fill the chip, D * R.
-                const bool wide8 = want == 8 || (want == 0 && D < kSolve10Lanes8Below * (ncu / 256.0));
-                if (wide8) { m->Ls = 8; m->cpl = 2; m->lam_occ = 3; } else { m->Ls = 2; m->cpl = 5; m->lam_occ = 2; }
-                m->persist = true;
-            } else if (dm.MK == 28) {
-                const bool wide32 = want == 32 || (want == 0 && (int64_t)D * R < kSolve28Lanes32Below * (ncu / 256.0));
-                // (16 x 2 needs 125 VGPRs: four waves per SIMD fit.  With three or more documents per slot the fourth wave pays -- config 4 at
-                // 50,000 documents 0.875 -> 0.861 ms per pass; at 25,000 / 12,500 documents it costs 4 % / 8 %: tools/ab_tuning.py, solve_waves)
-                const bool four = (int64_t)D * R >= kSolve28Waves4From * (ncu / 256.0);
-                if (wide32) { m->Ls = 32; m->cpl = 1; m->lam_occ = 4; } else { m->Ls = 16; m->cpl = 2; m->lam_occ = four ? 4 : 3; }
-                m->persist = true;
-            }
-        }
+    *n_features = (size_t)fo;
+    m->nalpha = tp.aoff[M]; m->GM = tp.mgoff[M];
+    return MMM_OK;
+}
+
+// the caller's arrays and what create_impl has formed from them on the host (rows: the rows of counts per modality, or empty)
+typedef std::vector<std::vector<unsigned short>> CountRows;
+struct CtmHostCorpus {
+    const int* V; const int64_t* doc_ptr; const int32_t* term; const int32_t* count;
+    const std::vector<CountPair>& tc; const std::vector<double>& Ndm; CountRows& rows;
+    const int32_t* features; size_t n_features; const double* alpha; const double* gamma0;
+};
+
+// create, step 4: the handle's buffers, and the corpus in every form the plan asks for (corpus_forms.h).  Every asynchronous copy reads
+// the caller's arrays, h's vectors or `post`, which all outlive the function's last wait for the stream.
+int ctm_upload(mmm_ctm* m, const CtmHostCorpus& h)
+{
+    mmm_ctx* ctx = m->ctx;
+    const CtmDims& dm = m->dm;
+    const int D = dm.D, M = dm.M, R = m->R, nalpha = m->nalpha, GM = m->GM;
+    const int64_t nnz = m->nnz;
+    for (int i = 0; i < M && m->tdense; ++i) {
+        hipError_t e_ = m->trows[i].alloc(h.rows[i].size());
+        if (e_ != hipSuccess) return mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(trows): %s", hipGetErrorString(e_));
+        if (hipMemcpy(m->trows[i].p, h.rows[i].data(), sizeof(unsigned short) * h.rows[i].size(), hipMemcpyHostToDevice) != hipSuccess)
+            return mmm_fail(ctx, MMM_ERR_HIP, "upload of the rows of counts failed");
     }
-    if (m->big) { m->Ls = 64; m->cpl = kBigSlots; m->persist = false; }      // ctm_big.cuh: lane l holds coordinates l + 64 q
-    const int Gs = MMM_WAVE / m->Ls;
-    m->grid_v = std::max(1, std::min((D + m->waves_s * Gs - 1) / (m->waves_s * Gs), ncu * 8));
-    // k_ctm_solve_cpl: persistent waves, each with a contiguous range of documents that its slots work through (a finished slot takes the
-    // range's next document): as many as are resident at once (lam_occ per SIMD), fewer when every document has a slot of its own.  (Round 5
-    // measured whole numbers of waves per SIMD with more documents than slots each for small shards: slower -- 6,249 documents of config 4:
-    // 200 us with one wave per SIMD against 188; the phase is issue-bound per SIMD and a half-filled wave costs a full trip.)
-    if (m->persist) {
-        const int blocks_full = (D + m->waves_s * Gs - 1) / (m->waves_s * Gs);      // every document a slot of its own
-        m->grid_v = std::max(1, std::min(blocks_full, ncu * m->lam_occ));
-        if (ctx->tune.solve_waves > 0) m->grid_v = std::max(1, std::min(blocks_full, ncu * ctx->tune.solve_waves));
-    }
-    // moment sums: whole 32-document tiles per block (a short last tile is padded to 32 and costs as much as a full one), at most 1024 blocks
-    {
-        const int tiles_per_block = std::max(1, (D + 32 * 1024 - 1) / (32 * 1024));
-        m->grid_m = std::max(1, (D + 32 * tiles_per_block - 1) / (32 * tiles_per_block));
-    }
-    if (ctx->tune.moment_blocks > 0) m->grid_m = ctx->tune.moment_blocks;
+    CountRows().swap(h.rows);      // (copied synchronously, or not wanted: the plan found a repeated term or a count beyond 16 bits)
     const size_t MK = dm.MK, DMK = (size_t)D * MK, Rz = (size_t)R;
-    m->nmom = 2 * dm.MK + dm.MK * dm.MK; m->nalpha = nalpha;
+    m->nmom = 2 * dm.MK + dm.MK * dm.MK;
     m->s_stats = (size_t)m->nmom + dm.GT + 16;
     m->s_llnum = (size_t)M + 8;
     m->h_active.assign(R, 1); m->n_hist.assign(R, 0); m->theta_state.assign(R, 0); m->theta_spill.resize(R);
-#define A(buf, n) do { hipError_t e_ = m->buf.alloc(n); if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(" #buf "): %s", hipGetErrorString(e_)); delete m; return rc; } } while (0)
-    A(doc_ptr, (size_t)M * (D + 1)); A(tc, (size_t)nnz); A(Ndm, (size_t)D * M); A(features, featv.size()); A(alpha, Rz * nalpha);
-    A(lambda, Rz * DMK); A(lambda_prev, Rz * DMK); A(nu, Rz * DMK); A(sumth, Rz * DMK); A(zeta, Rz * D * M); A(props, Rz * DMK); A(theta, (size_t)toff);
+#define A(buf, n) do { hipError_t e_ = m->buf.alloc(n); if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(" #buf "): %s", hipGetErrorString(e_)); return rc; } } while (0)
+    A(doc_ptr, (size_t)M * (D + 1)); A(tc, (size_t)nnz); A(Ndm, (size_t)D * M); A(features, h.n_features); A(alpha, Rz * nalpha);
+    A(lambda, Rz * DMK); A(lambda_prev, Rz * DMK); A(nu, Rz * DMK); A(sumth, Rz * DMK); A(zeta, Rz * D * M); A(props, Rz * DMK); A(theta, (size_t)m->theta_n);
     A(mu, Rz * MK); A(Sigma, Rz * MK * MK); A(invSigma, Rz * MK * MK); A(gamma, Rz * GM); A(Elnphi, Rz * GM); A(phi, Rz * GM);
     A(Eeff, Rz * dm.GT); A(expEeff, Rz * dm.GT); A(expEeff_prev, Rz * dm.GT); A(phieff, Rz * dm.GT);
     A(partial, m->wide ? 1 : Rz * m->grid_e * dm.GT); A(mompart, Rz * m->grid_m * m->nmom); A(stats, Rz * m->s_stats);
@@ -937,68 +794,58 @@ int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, c
     A(big_scratch, m->big ? Rz * 2 * (size_t)dm.MK * dm.MK : 1);
 #undef A
     hipStream_t st = ctx->stream;
-    MMM_HIP(ctx, hipMemcpyAsync(m->doc_ptr.p, doc_ptr, sizeof(int64_t) * M * (D + 1), hipMemcpyHostToDevice, st));
-    if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tc.p, tc.data(), sizeof(int2) * nnz, hipMemcpyHostToDevice, st));
-    if (D) MMM_HIP(ctx, hipMemcpyAsync(m->Ndm.p, Ndm.data(), sizeof(double) * D * M, hipMemcpyHostToDevice, st));
-    if (!featv.empty()) MMM_HIP(ctx, hipMemcpyAsync(m->features.p, featv.data(), sizeof(int) * featv.size(), hipMemcpyHostToDevice, st));
-    for (size_t r = 0; r < Rz; ++r) MMM_HIP(ctx, hipMemcpyAsync(m->alpha.p + r * nalpha, alpha, sizeof(double) * nalpha, hipMemcpyHostToDevice, st));
-    MMM_HIP(ctx, hipMemcpyAsync(m->gamma.p, gamma0, sizeof(double) * Rz * GM, hipMemcpyHostToDevice, st));
-    std::vector<int64_t> tptr;
-    std::vector<int2> tpost;
-    if (m->wide) {      // posting lists per (modality, term), documents ascending: the summation order of k_ctm_stats_terms
-        int nterms = 0;
-        std::vector<int> voff(M + 1, 0);
-        for (int i = 0; i < M; ++i) { voff[i + 1] = voff[i] + V[i]; }
-        nterms = voff[M];
-        tptr.assign((size_t)nterms + 1, 0);
-        for (int i = 0; i < M; ++i) {
-            const int64_t* dp = doc_ptr + (size_t)i * (D + 1);
-            for (int64_t e = dp[0]; e < dp[D]; ++e) tptr[(size_t)voff[i] + term[e] + 1]++;
-        }
-        for (int t = 0; t < nterms; ++t) tptr[(size_t)t + 1] += tptr[(size_t)t];
-        tpost.resize((size_t)nnz);
-        std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
-        for (int i = 0; i < M; ++i) {
-            const int64_t* dp = doc_ptr + (size_t)i * (D + 1);
-            for (int d = 0; d < D; ++d)
-                for (int64_t e = dp[d]; e < dp[d + 1]; ++e) tpost[(size_t)fill[(size_t)voff[i] + term[e]]++] = make_int2(d, count[e]);
-        }
-        m->nterms = nterms;
-        hipError_t e1 = m->term_ptr.alloc((size_t)nterms + 1), e2 = m->tpost.alloc((size_t)nnz), e3 = m->aexp.alloc(Rz * DMK);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(postings): out of memory"); delete m; return rc; }
-        MMM_HIP(ctx, hipMemcpyAsync(m->term_ptr.p, tptr.data(), sizeof(int64_t) * ((size_t)nterms + 1), hipMemcpyHostToDevice, st));
-        if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tpost.p, tpost.data(), sizeof(int2) * (size_t)nnz, hipMemcpyHostToDevice, st));
-        const int64_t avg = nnz / std::max(1, nterms);
-        m->stats_waves = 1;
-        while (m->stats_waves < 8 && avg / (m->stats_waves * 2) >= 128) m->stats_waves *= 2;
+    MMM_HIP(ctx, hipMemcpyAsync(m->doc_ptr.p, h.doc_ptr, sizeof(int64_t) * M * (D + 1), hipMemcpyHostToDevice, st));
+    if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tc.p, h.tc.data(), sizeof(int2) * nnz, hipMemcpyHostToDevice, st));
+    if (D) MMM_HIP(ctx, hipMemcpyAsync(m->Ndm.p, h.Ndm.data(), sizeof(double) * D * M, hipMemcpyHostToDevice, st));
+    if (h.n_features) MMM_HIP(ctx, hipMemcpyAsync(m->features.p, h.features, sizeof(int) * h.n_features, hipMemcpyHostToDevice, st));
+    for (size_t r = 0; r < Rz; ++r) MMM_HIP(ctx, hipMemcpyAsync(m->alpha.p + r * nalpha, h.alpha, sizeof(double) * nalpha, hipMemcpyHostToDevice, st));
+    MMM_HIP(ctx, hipMemcpyAsync(m->gamma.p, h.gamma0, sizeof(double) * Rz * GM, hipMemcpyHostToDevice, st));
+    Postings post;
+    if (m->wide) {      // posting lists per (modality, term): the summation order of k_ctm_stats_terms
+        post = postings_by_term(D, M, h.V, h.doc_ptr, h.term, h.count);
+        m->nterms = post.nterms;
+        hipError_t e1 = m->term_ptr.alloc((size_t)post.nterms + 1), e2 = m->tpost.alloc((size_t)nnz), e3 = m->aexp.alloc(Rz * DMK);
+        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(postings): out of memory");
+        MMM_HIP(ctx, hipMemcpyAsync(m->term_ptr.p, post.term_ptr.data(), sizeof(int64_t) * ((size_t)post.nterms + 1), hipMemcpyHostToDevice, st));
+        if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tpost.p, post.post.data(), sizeof(int2) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        m->stats_waves = post.stats_waves;
     }
     MMM_HIP(ctx, hipMemsetAsync(m->status.p, 0, sizeof(int) * R, st));
     MMM_HIP(ctx, hipMemsetAsync(m->nev_nu.p, 0, sizeof(int) * std::max<size_t>(Rz * D, 1), st));
     MMM_HIP(ctx, hipMemsetAsync(m->nev_lam.p, 0, sizeof(int) * std::max<size_t>(Rz * D, 1), st));
-    int rc = upload_active(m);
-    if (rc) { delete m; return rc; }
-    MMM_HIP(ctx, hipStreamSynchronize(st));
-    tp.features = m->features.p; tp.alpha = m->alpha.p;
-    // global N per modality and D (sum over ranks)
+    if (int rc = upload_active(m)) return rc;
+    MMM_HIP(ctx, hipStreamSynchronize(st));      // h.tc, h.Ndm and post must outlive their copies
+    m->tp.features = m->features.p; m->tp.alpha = m->alpha.p;
+    return MMM_OK;
+}
+
+// create, step 5: the global N per modality and D (sum over ranks), then the constructor state (MMCTM.jl:44-86): mu = 0, Sigma =
+// invSigma = I, theta = 1/K, Elnphi from gamma0, phi = gamma0 (deepcopy, MMCTM.jl:80), lambda = 0, nu = 1, zeta = update_ζ!
+int ctm_constructor_state(mmm_ctm* m)
+{
+    mmm_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const CtmDims& dm = m->dm;
+    const int D = dm.D, M = dm.M, R = m->R;
+    const size_t MK = dm.MK, DMK = (size_t)D * MK, Rz = (size_t)R;
+    int rc;
     {
         std::vector<double> h(m->hNm);
         h.push_back((double)D);
         MMM_HIP(ctx, hipMemcpyAsync(m->llnum.p, h.data(), sizeof(double) * (M + 1), hipMemcpyHostToDevice, st));
-        if ((rc = mmm_allreduce_sum(ctx, m->llnum.p, M + 1))) { delete m; return rc; }
+        if ((rc = mmm_allreduce_sum(ctx, m->llnum.p, M + 1))) return rc;
         MMM_HIP(ctx, hipMemcpyAsync(h.data(), m->llnum.p, sizeof(double) * (M + 1), hipMemcpyDeviceToHost, st));
         MMM_HIP(ctx, hipStreamSynchronize(st));
         m->Dglobal = h[M];
         MMM_HIP(ctx, hipMemcpyAsync(m->Nm.p, h.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
-        MMM_HIP(ctx, hipStreamSynchronize(st));
+        MMM_HIP(ctx, hipStreamSynchronize(st));      // h must outlive the copy
     }
-    // constructor state (MMCTM.jl:44-86): mu = 0, Sigma = invSigma = I, theta = 1/K, Elnphi from gamma0, phi = gamma0
-    // (deepcopy, MMCTM.jl:80), lambda = 0, nu = 1, zeta = update_ζ!
     std::vector<double> eye(Rz * MK * MK, 0.0);
     for (size_t r = 0; r < Rz; ++r) for (size_t i = 0; i < MK; ++i) eye[r * MK * MK + i * MK + i] = 1.0;
     MMM_HIP(ctx, hipMemsetAsync(m->mu.p, 0, sizeof(double) * Rz * MK, st));
     MMM_HIP(ctx, hipMemcpyAsync(m->Sigma.p, eye.data(), sizeof(double) * eye.size(), hipMemcpyHostToDevice, st));
     MMM_HIP(ctx, hipMemcpyAsync(m->invSigma.p, eye.data(), sizeof(double) * eye.size(), hipMemcpyHostToDevice, st));
-    MMM_HIP(ctx, hipStreamSynchronize(st));
+    MMM_HIP(ctx, hipStreamSynchronize(st));      // eye must outlive the copies
     if (DMK) {
         MMM_HIP(ctx, hipMemsetAsync(m->lambda.p, 0, sizeof(double) * Rz * DMK, st));
         MMM_HIP(ctx, hipMemsetAsync(m->lambda_prev.p, 0, sizeof(double) * Rz * DMK, st));
@@ -1006,13 +853,69 @@ int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, c
         hipLaunchKernelGGL(k_fill, dim3((unsigned)((Rz * DMK + 255) / 256)), dim3(256), 0, st, m->nu.p, Rz * DMK, 1.0);
     }
     MMM_LAUNCH_CHECK(ctx);
-    if ((rc = materialise_theta(m))) { delete m; return rc; }
+    if ((rc = materialise_theta(m))) return rc;
     Scope sc{0, R, nullptr};
-    if ((rc = run_mstep(m, sc, 0, 0, 1, 0))) { delete m; return rc; }                       // update_Elnϕ! on gamma0 (+ tables)
-    if (!m->immctm) MMM_HIP(ctx, hipMemcpyAsync(m->phi.p, m->gamma.p, sizeof(double) * Rz * GM, hipMemcpyDeviceToDevice, st));   // MMCTM.jl:80
-    if ((rc = run_estep(m, sc, F_ZETA, m->lambda.p, nullptr, nullptr))) { delete m; return rc; }
+    if ((rc = run_mstep(m, sc, 0, 0, 1, 0))) return rc;                       // update_Elnϕ! on gamma0 (+ tables)
+    if (!m->immctm) MMM_HIP(ctx, hipMemcpyAsync(m->phi.p, m->gamma.p, sizeof(double) * Rz * m->GM, hipMemcpyDeviceToDevice, st));   // MMCTM.jl:80
+    if ((rc = run_estep(m, sc, F_ZETA, m->lambda.p, nullptr, nullptr))) return rc;
     MMM_HIP(ctx, hipStreamSynchronize(st));
-    *out = m;
+    return MMM_OK;
+}
+
+int create_impl(mmm_ctx* ctx, int R, int D, int M, const int* K, const int* V, const double* alpha, const int64_t* doc_ptr, const int32_t* term,
+                const int32_t* count, const int* n_feat, const int* J, const int32_t* features, const double* gamma0,
+                const mmm_solver_opts* opts, mmm_ctm** out)
+{
+    // 1. the arguments, then the corpus
+    if (!ctx) return MMM_ERR_ARG;
+    MMM_CHECK(ctx, out && K && V && alpha && doc_ptr && gamma0, "mmm_ctm_create: NULL argument");
+    MMM_CHECK(ctx, D >= 0 && M >= 1 && M <= kMaxM && R >= 1, "mmm_ctm_create: bad sizes D=%d M=%d (M <= %d) R=%d", D, M, kMaxM, R);
+    *out = nullptr;
+    MMM_HIP(ctx, hipSetDevice(ctx->device));
+    // the theta phase as far as the dimensions decide it -- or the refusal of the shape, before the corpus is looked at (nnz_m: offsets only)
+    int64_t nnz_m[kMaxM];
+    for (int i = 0; i < M; ++i) nnz_m[i] = doc_ptr[(size_t)i * (D + 1) + D] - doc_ptr[(size_t)i * (D + 1)];
+    const int ncu = mmm_geo_cus(ctx);      // the CU count the geometry (and so the association of the cross-document sums) is derived from
+    const CtmThetaShape theta = ctm_theta_plan(ctx->tune, ncu, D, M, K, V, nnz_m);
+    if (theta.refusal) return mmm_fail(ctx, theta.refusal, "%s", theta.why.c_str());
+    std::unique_ptr<mmm_ctm> guard(new mmm_ctm());      // every early return below (MMM_HIP, ...) destroys the model and its buffers
+    mmm_ctm* m = guard.get();
+    m->ctx = ctx; m->R = R;
+    CtmDims& dm = m->dm;
+    dm.D = D; dm.M = M; dm.koff[0] = 0; dm.goff[0] = 0;
+    int64_t toff = 0;
+    for (int i = 0; i < M; ++i) {
+        dm.K[i] = K[i]; dm.V[i] = V[i];
+        dm.koff[i + 1] = dm.koff[i] + K[i]; dm.goff[i + 1] = dm.goff[i] + K[i] * V[i];
+        dm.estart[i] = doc_ptr[(size_t)i * (D + 1)];
+        dm.toff[i] = toff;
+        m->nnzm[i] = nnz_m[i];
+        toff += m->nnzm[i] * K[i];
+    }
+    dm.MK = dm.koff[M]; dm.GT = dm.goff[M];
+    m->nnz = doc_ptr[(size_t)(M - 1) * (D + 1) + D]; m->theta_n = toff;
+    m->h_doc_ptr.assign(doc_ptr, doc_ptr + (size_t)M * (D + 1));
+    std::vector<CountPair> tc;
+    std::vector<double> Ndm;
+    if (int rc = check_corpus(ctx, D, M, V, doc_ptr, term, count, tc, Ndm, m->hNm)) return rc;
+    // 2. what the plan needs to know about the corpus.  Where the dimensions leave the rows of counts open they are packed now, and the packing
+    // sweep gathers the facts: beside its scattered stores the scan is free, in the sequential checking sweep it cost 6 % of a create
+    CorpusFacts facts[kMaxM];
+    CountRows rows;
+    for (int i = 0; i < M && theta.rows_shape; ++i)
+        rows.push_back(pack_count_rows<unsigned short>(D, count_row_slots16(theta.plan.tSL[i]), kRows16Spare, doc_ptr + (size_t)i * (D + 1), term, count, V[i], &facts[i]));
+    // 3. every build and every launch geometry (the shapes without a build were refused above)
+    static_cast<CtmPlan&>(*m) = ctm_plan(ctx->tune, ncu, R, D, M, K, theta, facts).plan;
+    // 3b. the topics descriptor, the caller's choices
+    size_t n_features = 0;
+    if (int rc = topics_descriptor(m, n_feat, J, features, &n_features)) return rc;
+    m->tune = ctx->tune;
+    mmm_solver_opts so; mmm_solver_opts_default(&so);
+    if (opts) so = *opts;
+    m->opt = SolveOpts{so.xtol_rel, so.xtol_abs, so.nu_lower, so.xtol_rule, so.max_eval > 0 ? so.max_eval : 2000};
+    if (int rc = ctm_upload(m, CtmHostCorpus{V, doc_ptr, term, count, tc, Ndm, rows, features, n_features, alpha, gamma0})) return rc;      // 4.
+    if (int rc = ctm_constructor_state(m)) return rc;                                                                                // 5.
+    *out = guard.release();
     mmm_ctx_model_created(ctx);
     return MMM_OK;
 }

@@ -38,12 +38,11 @@
 #include "mmm_logtab.h"
 #include "mmm_exptab.h"
 #include "mmm_internal.h"
+#include "create_plan.h"
 
 namespace {
 
-constexpr int kWavesPerBlock = 4;                    // stage kernels
 constexpr int kBlock = kWavesPerBlock * MMM_WAVE;
-constexpr int kMaxWavesE = 12;                       // fused E-step kernel: up to 768 threads
 
 struct LdaDev {
     int D, V, K;
@@ -224,18 +223,17 @@ struct PinnedCtl {
     ~PinnedCtl() { if (p) (void)hipHostFree(p); }
 };
 
-struct mmm_lda {
+struct mmm_lda : LdaPlan {      // the plan the handle was created with (create_plan.h): builds, geometry, LDS sizes
     mmm_ctx* ctx = nullptr;
     mmm_tuning_opts tune{};      // the caller's choices at create time (mmm_ctx_set_tuning)
-    int D = 0, V = 0, K = 0, KP = 0, L = 16;
+    int D = 0, V = 0, K = 0;
     int64_t nnz = 0;
     double alpha = 0, eta = 0;
     double Nglobal = 0, Dglobal = 0;
     DevBuf<int64_t> doc_ptr; DevBuf<int2> tc, tc_ell;
     DevBuf<unsigned short> cnt16;   // the rows as 16-bit counts, when every count fits (then cnt_dense is not built)
     DevBuf<int> cnt_dense;      // dense rows [D][16 SL] of counts (k_lda_estep_dense), or empty
-    bool dense = false; int SL = 0, SLs = 0; size_t lds_d = 0; bool attr_d = false;     // SL: term slots per lane of a 16-lane group; SLs: as stored (LdaDev::Vp / 16)
-    bool drows = false;         // cnt_dense exists (dense-row E-step build, or rows for the single-step build and the ll blocks)
+    bool attr_d = false;
     DevBuf<double> lambda[3], Elnbeta[3], expElnbeta[3], beta[3], gamma[3], Elntheta[3];
     DevBuf<double> theta, phi;
     DevBuf<double> partial, stats[2], scratch, llpart, llpart2, elbopart, ll_hist;
@@ -257,8 +255,6 @@ struct mmm_lda {
     bool stop_seen = false;     // the device stop flag may be set
     bool lag_ll = true;         // the passes in flight evaluate the ll one pass late (training); false: frozen-topic passes
     bool phi_table_beta = false; // phi of the current state is exp(Elntheta) .* beta normalised (unsmoothed_update_ϕ!, LDA.jl:226)
-    bool single_step = false;   // one step per wave: the grid covers every document
-    bool wide = false;          // K*V tables larger than LDS: k_lda_estep_wide + k_lda_stats_terms, tables through L2
     DevBuf<int64_t> term_ptr;           // wide: the postings of term v are tpost[term_ptr[v] .. term_ptr[v+1])
     DevBuf<int2> tpost;                 // (document, count), documents ascending within a term
     DevBuf<double> aexp;                // wide: exp(Elntheta_t), D x KP, written by the document sweep for the term sweep
@@ -270,10 +266,7 @@ struct mmm_lda {
     DevBuf<double> tabT;                // wide: [2][V][KP] term-major copies of the pass's exp(Elnbeta) and beta tables
     int stats_waves = 1;                // waves per term block of k_lda_stats_terms
     bool attr_big = false, attr_bigs = false;
-    int grid_e = 1, waves_e = 8, grid_s = 1;
-    size_t lds_e = 0, lds_tab = 0;
-    bool block_stats = false;   // single-step passes without the E-step ll take k_lda_estep_block (statistics as a block product, no slabs)
-    size_t lds_b = 0; bool attr_b[2] = {false, false};      // its dynamic LDS: table | r | a
+    bool attr_b[2] = {false, false};
     // ILDA (src/ILDA.jl): feature-factorised topics; the V x K rings then hold the effective tables
     bool ilda = false;
     IldaDesc ids{};
@@ -308,13 +301,11 @@ struct mmm_lda {
 
 namespace {
 
-int pick_kp(int K)
-{
-    static const int opts[] = {2, 4, 6, 8, 10, 12, 16, 20, 24, 32};
-    for (int o : opts) if (K <= o) return o;
-    if (K <= 64 * kLdaSlots) return (K + 1) & ~1;      // 33..256 topics: the rolled-loop kernels (k_lda_estep_big, k_lda_stats_big), wide path only
-    return -1;
-}
+static_assert(kPlanWave == MMM_WAVE && kLdaTopicSlots == kLdaSlots && sizeof(CountPair) == sizeof(int2), "create_plan.h / corpus_forms.h restate these");
+// the host packer and the kernels' row_slot (lda_rows.cuh) place term w of a row alike: lane w % 16, the lane's slot w / 16
+constexpr int device_row_slot(int w, int slp) { return (w & 15) * slp + (w >> 4); }      // row_slot's expression, as a constant expression
+constexpr bool row_slots_agree(int slots) { for (int w = 0; w < 16 * slots; ++w) if (count_row_slot(w, slots) != device_row_slot(w, slots)) return false; return true; }
+static_assert(row_slots_agree(2) && row_slots_agree(3) && row_slots_agree(4) && row_slots_agree(6) && row_slots_agree(8), "corpus_forms.h packs rows as lda_rows.cuh reads them");
 
 #define MMM_KP_SWITCH(m, ...)                                                                                   \
     switch ((m)->KP) {                                                                                          \
@@ -405,9 +396,6 @@ int go_dense(mmm_lda* m, const EstepArgs& a)
         return MMM_OK;
     } else return mmm_fail(m->ctx, MMM_ERR_UNSUPPORTED, "LDA: no dense-row build for KP=%d SL=%d", KPV, SLV);
 }
-
-// term slots per lane of the dense-row build that covers V terms (0: none)
-int dense_slots(int V) { return V <= 32 ? 2 : (V <= 48 ? 3 : (V <= 96 ? 6 : (V <= 128 ? 8 : 0))); }
 
 // RB: a batched pass (split pipeline; the ll rides in the reduce launch, so a.do_ll = 0 and the wide path never comes here)
 template <bool RB = false>
@@ -933,118 +921,19 @@ extern "C" int mmm_diag_red_stamps(unsigned long long out[32])
 
 extern "C" {
 
-constexpr int kMinWavesSingle = 4;      // single-step build: fewest waves per block the library picks by itself (shard sizes: profiles/r05_lda_small_shards.txt)
+// what mmm_ilda_create adds to the arguments (I = 0: plain LDA)
+struct IldaSpec { int I; const int* J; const double* eta; const int32_t* features; int SJ; };
 
-static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, double eta, const int64_t* doc_ptr, const int32_t* term,
-                           const int32_t* count, const double* lambda0, int I, const int* J, const double* eta_i, const int32_t* features,
-                           mmm_lda** out, int R = 1)
+// create, step 4: the handle's buffers, and the corpus in every form the plan asks for (corpus_forms.h).  The host vectors below are the
+// sources of asynchronous copies and live to the end of the function, which waits for the stream.
+static int lda_upload(mmm_lda* m, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const std::vector<CountPair>& tc, const double* lambda0,
+                      const IldaSpec& il)
 {
-    if (!ctx) return MMM_ERR_ARG;
-    MMM_CHECK(ctx, out && doc_ptr && lambda0, "mmm_lda_create: NULL argument");
-    const bool ilda = I > 0;
-    int SJ = 0;
-    if (ilda) {
-        MMM_CHECK(ctx, J && eta_i && features, "mmm_ilda_create: NULL argument");
-        if (I > kIldaMaxI) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ilda_create: I=%d features (max %d)", I, kIldaMaxI);
-        for (int i = 0; i < I; ++i) { MMM_CHECK(ctx, J[i] >= 1, "mmm_ilda_create: J[%d] < 1", i); SJ += J[i]; }
-        if (SJ > kIldaMaxSJ) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ilda_create: sum(J)=%d (max %d)", SJ, kIldaMaxSJ);
-        for (int i = 0; i < I; ++i) for (int v = 0; v < V; ++v)
-            MMM_CHECK(ctx, features[(size_t)i * V + v] >= 0 && features[(size_t)i * V + v] < J[i], "mmm_ilda_create: feature value out of range (i=%d v=%d)", i, v);
-    }
-    MMM_CHECK(ctx, D >= 0 && V >= 1 && K >= 1, "mmm_lda_create: bad sizes D=%d V=%d K=%d", D, V, K);
-    *out = nullptr;
-    const int KP = pick_kp(K);
-    if (KP < 0) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_create: K=%d not supported (max 256: an LDS column block of 512 K bytes per wave)", K);
-    const int64_t nnz = doc_ptr[D];
-    MMM_CHECK(ctx, doc_ptr[0] == 0 && nnz >= 0 && (nnz == 0 || (term && count)), "mmm_lda_create: bad CSR");
-    std::vector<int2> tc((size_t)nnz);
-    for (int d = 0; d < D; ++d) MMM_CHECK(ctx, doc_ptr[d + 1] >= doc_ptr[d], "mmm_lda_create: doc_ptr not monotone at %d", d);
-    for (int64_t e = 0; e < nnz; ++e) {
-        MMM_CHECK(ctx, term[e] >= 0 && term[e] < V && count[e] >= 0, "mmm_lda_create: entry %lld out of range (term %d, count %d)", (long long)e, term[e], count[e]);
-        tc[(size_t)e] = make_int2(term[e], count[e]);
-    }
-    const int L = (K <= 15) ? 16 : (K <= 31 ? 32 : 64);
-    const int G = MMM_WAVE / L;
-    const int ncu = mmm_geo_cus(ctx);      // the CU count the geometry (and so the association of the cross-document sums) is derived from
-    // waves per block of the fused kernel: as many as fit 160 KiB of LDS next to the two tables, at most 8
-    const size_t tabB = (size_t)KP * V * sizeof(double);
-    // Small corpora (every document resident at once): 6-wave blocks, two per CU, one step per wave with the <= 168-VGPR
-    // single-step build (3 waves per SIMD).  Larger corpora: 8-wave blocks, one per CU, grid-stride steps (2 waves per SIMD).
-    // dense-row E-step (k_lda_estep_dense): a dense corpus (at least half of the D x V entries present, no term listed twice in a
-    // document) of at least 192 documents per CU, topics and vocabulary within the register budget of a lane (SL KP <= 64
-    // doubles).  MMM_LDA_DENSE=1 takes it for any corpus that has the shape (tests), 0 never.
-    // Rows of counts (drows): a dense corpus over <= 128 terms is also kept as rows of 16 SL int32 counts -- 4 bytes per term slot against
-    // 8 per nonzero -- which the single-step E-step build (96-term vocabularies) and the ll blocks read instead of the padded (term,count)
-    // rows: BASELINE config 2 21.2 -> 19.9 us per iteration on the same box.  MMM_LDA_DROWS=0 keeps the (term,count) rows (A/B).
-    bool dense = false, drows = false, dup_terms = false;
-    const int SL = dense_slots(V);
-    {
-        const int build = ctx->tune.lda_build;
-        const int dmode = build == MMM_BUILD_DENSE ? 1 : (build == MMM_BUILD_AUTO ? -1 : 0);
-        const bool drows_env = !mmm_off(ctx->tune, MMM_OFF_LDA_COUNT_ROWS);
-        const bool rshape = SL > 0 && L == 16 && D > 0 && build != MMM_BUILD_WIDE;          // rows of counts make sense
-        const bool shape = rshape && KP >= 4 && KP * SL <= 64;                               // ... and the dense-row E-step build exists
-        const bool dense_enough = 2 * nnz >= (int64_t)D * V;
-        bool dup = false;
-        const bool block_shape = L == 16 && KP <= 12 && V <= 96;      // could be single-step: k_lda_estep_block needs every (document, term) listed once
-        if ((rshape && ((shape && dmode != 0) || (drows_env && dense_enough))) || block_shape) {
-            std::vector<int> seen((size_t)V, -1);
-            for (int d = 0; d < D && !dup; ++d)
-                for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) { if (seen[(size_t)term[e]] == d) { dup = true; break; } seen[(size_t)term[e]] = d; }
-        }
-        // measured on MI355X (K = 10, V = 96; E-step launch, dense rows vs the CSR sweep): 10k documents 12.4 vs 10.9 us (the single-step build),
-        // 15k 12.8 vs 14.1, 20k 16.7 vs 19.3, 40k 20.2 vs 27.7, 640k 190 vs 380 -- every corpus beyond the single-step build's reach
-        // (profiles/experiments/r03_sweeps/dense_crossover.sh; round 2's build only paid from 49k documents: its epilogue cost 19 us)
-        const bool big = D > 12 * G * ncu;
-        const bool off32 = (int64_t)D * K * 8 < ((int64_t)1 << 32) && (int64_t)D * 16 * (SL + 1) * 4 < ((int64_t)1 << 32);   // the build's 32-bit byte offsets
-        dense = shape && !dup && off32 && dmode != 0 && (dmode > 0 || (big && dense_enough));
-        drows = drows_env && rshape && !dup && dense_enough;
-        dup_terms = dup;
-    }
-    const bool small = !dense && (V <= 96) && KP <= 12 && ((D + 12 * G - 1) / (12 * G) <= ncu) && ctx->tune.grid_blocks == 0;
-    // single-step build: just enough waves per block to cover the corpus with one block per CU (fewer co-resident waves
-    // per SIMD = shorter step); mmm_tuning_opts.waves_per_block pins the count (more blocks than CUs are fine: two blocks share a CU)
-    const int swaves = ctx->tune.waves_per_block > 0 ? std::min(12, ctx->tune.waves_per_block) : std::max(kMinWavesSingle, std::min(12, (D + G * ncu - 1) / (G * ncu)));
-    int waves = small ? swaves : 8;
-    auto lds_for = [&](int w) { return tabB * (2 + w) + (size_t)2 * w * G * KP * sizeof(double); };
-    while (waves > 1 && lds_for(waves) > (small ? 150 : 80) * 1024) --waves;
-    // tables + one slab beyond LDS: the wide path (k_lda_estep_wide).  It also takes K > 24: the LDS kernel's 32-topic build
-    // spills (10k x 96-term documents, K = 32: 264 us per iteration against 189).  lda_build = MMM_BUILD_WIDE forces it, MMM_BUILD_SPARSE /
-    // _DENSE avoid it where the LDS kernels can run (tests, A/B).
-    const bool wide = lds_for(waves) > 160 * 1024 || KP > 32 || (ctx->tune.lda_build == MMM_BUILD_WIDE) || (ctx->tune.lda_build == MMM_BUILD_AUTO && KP >= 32);
-    if (R > 1 && wide) {
-        const char* why = ctx->tune.lda_build == MMM_BUILD_WIDE ? "lda_build = MMM_BUILD_WIDE takes the wide path (tables through L2)"
-                        : KP > 32 ? "K > 32 topics take the wide path (no LDS build)"
-                        : ctx->tune.lda_build == MMM_BUILD_AUTO && KP >= 32 ? "K >= 25 topics take the wide path under MMM_BUILD_AUTO"
-                        : "the K x V tables and one slab exceed LDS (wide path)";
-        return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_lda_create_batch: K=%d V=%d: %s, which has no batched build -- fit such shapes on single handles", K, V, why);
-    }
-
-    MMM_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<mmm_lda> guard(new mmm_lda());      // every early return below (MMM_HIP, ...) destroys the model and its buffers
-    mmm_lda* m = guard.get();
-    m->tune = ctx->tune;
-    m->ctx = ctx; m->D = D; m->V = V; m->K = K; m->KP = KP; m->L = L; m->nnz = nnz; m->alpha = alpha; m->eta = eta;
-    m->R = R; m->rep_t.assign((size_t)R, 0); m->rep_hist.assign((size_t)R, 0);
-    m->waves_e = waves; m->lds_e = wide ? 0 : lds_for(waves); m->lds_tab = tabB; m->wide = wide;
-    m->dense = dense && !wide; m->SL = SL; m->drows = (dense || drows) && !wide;
-    if (!wide && ctx->tune.waves_per_block > 0) { const int w = ctx->tune.waves_per_block; if (w >= 1 && w <= (small ? kMaxWavesE : 8) && lds_for(w) <= 160 * 1024) { m->waves_e = w; m->lds_e = lds_for(w); } }
-    const size_t VK = (size_t)V * K, KD = (size_t)K * D, Rs = (size_t)R;
-    const int docs_per_block = m->waves_e * G;
-    const int blocks_per_cu = wide ? 8 : std::max(1, std::min<int>((small ? 12 : 8) / m->waves_e, (int)((160 * 1024) / m->lds_e)));
-    m->single_step = !wide && small && (int64_t)m->waves_e * G * ncu * blocks_per_cu >= D;      // the grid covers every document at once
-    m->grid_e = std::max(1, std::min((D + docs_per_block - 1) / docs_per_block, ncu * blocks_per_cu));
-    if (wide) m->grid_e = std::max(1, std::min((D + kWavesPerBlock - 1) / kWavesPerBlock, ncu * blocks_per_cu));     // wave per document
-    if (ctx->tune.grid_blocks > 0) m->grid_e = ctx->tune.grid_blocks;
-    if ((int64_t)m->grid_e * docs_per_block < D) m->single_step = false;
-    // statistics as a block product (k_lda_estep_block): the single-step geometry above is decided by the slab build's LDS, so that grid,
-    // waves and the association of the cross-block sums are the same whichever build runs; the launch itself asks for what it uses
-    m->block_stats = m->single_step && L == 16 && KP <= 12 && !dup_terms && !mmm_off(ctx->tune, MMM_OFF_LDA_BLOCK_STATS);
-    m->lds_b = sizeof(double) * ((size_t)KP * V + (size_t)m->waves_e * G * (((size_t)V + 15) & ~(size_t)15) + (size_t)m->waves_e * G * KP);
-    if (m->dense)      // [16 SL][KP] table | [waves][K][V] slabs | [waves][G][KP] a_k | [waves][64][KP] gamma sums
-        m->lds_d = sizeof(double) * ((size_t)16 * SL * KP + (size_t)m->waves_e * 16 * SL * KP + (size_t)m->waves_e * G * KP + (size_t)m->waves_e * MMM_WAVE * KP);
-    if (m->dense && m->lds_d > 160 * 1024) { m->dense = false; m->drows = drows && !wide; }      // no dense-row build: rows only if the corpus is dense enough
-    m->grid_s = std::max(1, std::min((D + kWavesPerBlock - 1) / kWavesPerBlock, ncu * 4));
+    mmm_ctx* ctx = m->ctx;
+    const int D = m->D, V = m->V, K = m->K, KP = m->KP, I = il.I, SJ = il.SJ;
+    const int64_t nnz = m->nnz;
+    const bool wide = m->wide, ilda = I > 0;
+    const size_t VK = (size_t)V * K, KD = (size_t)K * D, Rs = (size_t)m->R;
     const int grid_max = std::max(m->grid_e, m->grid_s);
 #define A(buf, n) do { hipError_t e_ = m->buf.alloc(n); if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(" #buf "): %s", hipGetErrorString(e_)); return rc; } } while (0)
     A(doc_ptr, (size_t)D + 1); A(tc, (size_t)nnz);
@@ -1057,81 +946,50 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     A(partial, wide ? 1 : Rs * m->grid_e * VKp); A(stats[0], Rs * (VKp + 16)); A(stats[1], Rs * (VKp + 16)); A(scratch, VK + 16); A(llpart, Rs * grid_max);
     A(llpart2, Rs * 1024); A(elbopart, (size_t)m->grid_s * 5 + 8 * Rs);
     A(ctl, Rs); A(cells, 2 * 1024);
-    if (m->single_step && !ilda) A(aexp_next, std::max(KD, (size_t)K));
+    if (m->keeps_aexp_next) A(aexp_next, std::max(KD, (size_t)K));
     if (ilda) {
         A(fcells, (size_t)2 * 512 * 16);
         A(features, (size_t)I * V);
         for (int i = 0; i < 3; ++i) { A(ilam[i], (size_t)SJ * K); A(iEln[i], (size_t)SJ * K); A(ibeta[i], (size_t)SJ * K); }
     }
-#undef A
     hipStream_t st = ctx->stream;
     MMM_HIP(ctx, hipMemcpyAsync(m->doc_ptr.p, doc_ptr, sizeof(int64_t) * (D + 1), hipMemcpyHostToDevice, st));
     if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tc.p, tc.data(), sizeof(int2) * nnz, hipMemcpyHostToDevice, st));
-    std::vector<int64_t> tptr;
-    std::vector<int2> tpost;
-    if (wide) {     // postings by term, documents ascending within a term (counting sort): the summation order of k_lda_stats_terms
-        tptr.assign((size_t)V + 1, 0);
-        for (int64_t e = 0; e < nnz; ++e) tptr[(size_t)term[e] + 1]++;
-        for (int v = 0; v < V; ++v) tptr[(size_t)v + 1] += tptr[(size_t)v];
-        tpost.resize((size_t)nnz);
-        std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
-        for (int d = 0; d < D; ++d)
-            for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) tpost[(size_t)fill[(size_t)term[e]]++] = make_int2(d, count[e]);
+    Postings post;
+    if (wide) {     // postings by term: the summation order of k_lda_stats_terms
+        post = postings_by_term(D, 1, &V, doc_ptr, term, count);
         hipError_t e1 = m->term_ptr.alloc((size_t)V + 1), e2 = m->tpost.alloc((size_t)nnz), e3 = m->aexp.alloc((size_t)KP * D), e4 = m->tabT.alloc((size_t)2 * V * KP);
         if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(postings): out of memory"); return rc; }
-        MMM_HIP(ctx, hipMemcpyAsync(m->term_ptr.p, tptr.data(), sizeof(int64_t) * ((size_t)V + 1), hipMemcpyHostToDevice, st));
-        if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tpost.p, tpost.data(), sizeof(int2) * (size_t)nnz, hipMemcpyHostToDevice, st));
-        // waves per term block: segments of >= 128 postings on average, at most 8
-        const int64_t avg = nnz / std::max(1, V);
-        m->stats_waves = 1;
-        while (m->stats_waves < 8 && avg / (m->stats_waves * 2) >= 128) m->stats_waves *= 2;
+        MMM_HIP(ctx, hipMemcpyAsync(m->term_ptr.p, post.term_ptr.data(), sizeof(int64_t) * ((size_t)V + 1), hipMemcpyHostToDevice, st));
+        if (nnz) MMM_HIP(ctx, hipMemcpyAsync(m->tpost.p, post.post.data(), sizeof(int2) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        m->stats_waves = post.stats_waves;
     }
-    const bool rows16_env = !mmm_off(ctx->tune, MMM_OFF_LDA_ROWS16);
-    int maxcount = 0;
-    for (int64_t e = 0; e < nnz; ++e) maxcount = std::max(maxcount, count[e]);
-    if (m->drows && rows16_env && maxcount < 65536) {
-        m->SLs = (SL + 1) & ~1;          // lane-major rows (LdaDev::dense): an even number of 16-bit slots per lane
-        const int Vp = 16 * m->SLs;
-        std::vector<unsigned short> rows((size_t)D * Vp + 8, 0);       // (+ 16 bytes: the ll blocks read 16 bytes from a lane's first slot)
-        for (int d = 0; d < D; ++d)
-            for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) rows[(size_t)d * Vp + (term[e] & 15) * m->SLs + (term[e] >> 4)] = (unsigned short)count[e];
-        hipError_t e_ = m->cnt16.alloc(rows.size());
-        if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(cnt16): %s", hipGetErrorString(e_)); return rc; }
+    if (m->drows && m->rows16) {
+        const std::vector<unsigned short> rows = pack_count_rows<unsigned short>(D, m->SLs, kRows16Spare, doc_ptr, term, count);
+        A(cnt16, rows.size());
         MMM_HIP(ctx, hipMemcpyAsync(m->cnt16.p, rows.data(), sizeof(unsigned short) * rows.size(), hipMemcpyHostToDevice, st));
-        MMM_HIP(ctx, hipStreamSynchronize(st));
+        MMM_HIP(ctx, hipStreamSynchronize(st));      // rows must outlive the copy
     } else if (m->drows) {
-        m->SLs = SL;
-        const int Vp = 16 * SL;
-        std::vector<int> rows((size_t)D * Vp, 0);
-        for (int d = 0; d < D; ++d)
-            for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) rows[(size_t)d * Vp + (term[e] & 15) * SL + (term[e] >> 4)] = count[e];
-        hipError_t e_ = m->cnt_dense.alloc(rows.size());
-        if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(cnt_dense): %s", hipGetErrorString(e_)); return rc; }
+        const std::vector<int> rows = pack_count_rows<int>(D, m->SLs, 0, doc_ptr, term, count);
+        A(cnt_dense, rows.size());
         MMM_HIP(ctx, hipMemcpyAsync(m->cnt_dense.p, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st));
-        MMM_HIP(ctx, hipStreamSynchronize(st));
+        MMM_HIP(ctx, hipStreamSynchronize(st));      // rows must outlive the copy
     }
-    std::vector<int2> ell;
-    {   // padded rows for the ll blocks (V <= 128 slots, no duplicate terms: then a document always fits its row)
-        int64_t maxW = 0;
-        for (int d = 0; d < D; ++d) maxW = std::max<int64_t>(maxW, doc_ptr[d + 1] - doc_ptr[d]);
-        // (the ll blocks take their lanes per document from KP, the rows of counts serve 16-lane groups only: K = 13..15 needs the padded rows too)
-        if (V <= 128 && maxW <= V && D > 0 && !wide && (!m->drows || m->KP > 15)) {
-            ell.assign((size_t)D * V, make_int2(-1, 0));
-            for (int d = 0; d < D; ++d)
-                for (int64_t e = doc_ptr[d]; e < doc_ptr[d + 1]; ++e) ell[(size_t)d * V + (e - doc_ptr[d])] = tc[(size_t)e];
-            hipError_t e_ = m->tc_ell.alloc(ell.size());
-            if (e_ != hipSuccess) { int rc = mmm_fail(ctx, MMM_ERR_HIP, "hipMalloc(tc_ell): %s", hipGetErrorString(e_)); return rc; }
-            MMM_HIP(ctx, hipMemcpyAsync(m->tc_ell.p, ell.data(), sizeof(int2) * ell.size(), hipMemcpyHostToDevice, st));
-        }
+    std::vector<CountPair> ell;
+    if (m->padded_rows) {
+        ell = padded_term_rows(D, V, doc_ptr, term, count);
+        A(tc_ell, ell.size());
+        MMM_HIP(ctx, hipMemcpyAsync(m->tc_ell.p, ell.data(), sizeof(int2) * ell.size(), hipMemcpyHostToDevice, st));
     }
+#undef A
     if (!ilda) MMM_HIP(ctx, hipMemcpyAsync(m->lambda[0].p, lambda0, sizeof(double) * VK * Rs, hipMemcpyHostToDevice, st));
     else {
         m->ilda = true;
         IldaDesc& ds = m->ids;
         ds.I = I; ds.V = V; ds.K = K; ds.SJ = SJ; ds.joff[0] = 0;
-        for (int i = 0; i < I; ++i) { ds.J[i] = J[i]; ds.joff[i + 1] = ds.joff[i] + J[i]; ds.eta[i] = eta_i[i]; }
+        for (int i = 0; i < I; ++i) { ds.J[i] = il.J[i]; ds.joff[i + 1] = ds.joff[i] + il.J[i]; ds.eta[i] = il.eta[i]; }
         ds.features = m->features.p;
-        MMM_HIP(ctx, hipMemcpyAsync(m->features.p, features, sizeof(int) * (size_t)I * V, hipMemcpyHostToDevice, st));
+        MMM_HIP(ctx, hipMemcpyAsync(m->features.p, il.features, sizeof(int) * (size_t)I * V, hipMemcpyHostToDevice, st));
         MMM_HIP(ctx, hipMemcpyAsync(m->ilam[0].p, lambda0, sizeof(double) * (size_t)SJ * K, hipMemcpyHostToDevice, st));
         for (int i = 0; i < 3; ++i) MMM_HIP(ctx, hipMemsetAsync(m->lambda[i].p, 0, sizeof(double) * VK, st));      // unused for ILDA
     }
@@ -1140,12 +998,22 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     if (ilda) MMM_HIP(ctx, hipMemsetAsync(m->fcells.p, 0, sizeof(unsigned long long) * 2 * 512 * 16, st));
     if (!wide) MMM_HIP(ctx, hipMemsetAsync(m->partial.p, 0, sizeof(double) * Rs * m->grid_e * VKp, st));      // pad entries are never written
     if (KD) MMM_HIP(ctx, hipMemsetAsync(m->theta.p, 0, sizeof(double) * KD, st));
-    MMM_HIP(ctx, hipStreamSynchronize(st));   // tc (host vector) must outlive the copy
-    // constructor state (LDA.jl:36-49): Elnbeta from lambda0; gamma = 1 -> Elntheta; phi = 1/K
-    for (size_t r = 0; r < Rs && !ilda; ++r)
-        hipLaunchKernelGGL(k_lda_topic, dim3(K), dim3(256), 0, st, V, eta, (const double*)nullptr, m->lambda[0].p + r * VK, m->Elnbeta[0].p + r * VK, m->expElnbeta[0].p + r * VK,
+    MMM_HIP(ctx, hipStreamSynchronize(st));   // tc, post and ell must outlive their copies
+    return MMM_OK;
+}
+
+// create, step 5: constructor state (LDA.jl:36-49): Elnbeta from lambda0; gamma = 1 -> Elntheta; phi = 1/K; the global N and D
+static int lda_constructor_state(mmm_lda* m)
+{
+    mmm_ctx* ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const int D = m->D, V = m->V, K = m->K;
+    const int64_t nnz = m->nnz;
+    const size_t VK = (size_t)V * K, KD = (size_t)K * D, Rs = (size_t)m->R;
+    for (size_t r = 0; r < Rs && !m->ilda; ++r)
+        hipLaunchKernelGGL(k_lda_topic, dim3(K), dim3(256), 0, st, V, m->eta, (const double*)nullptr, m->lambda[0].p + r * VK, m->Elnbeta[0].p + r * VK, m->expElnbeta[0].p + r * VK,
                            m->beta[0].p + r * VK, 0);
-    if (ilda)
+    if (m->ilda)
         hipLaunchKernelGGL(k_ilda_mstep, dim3(K), dim3(64 * m->ids.I), 0, st, m->ids, 1, (const double*)nullptr, m->ilam[0].p, m->iEln[0].p, m->ibeta[0].p,
                            m->Elnbeta[0].p, m->expElnbeta[0].p, m->beta[0].p, (const int*)nullptr, 0, ReduceArgs{}, 0);      // ILDA.jl:36-40 (+ tables)
     if (KD) {
@@ -1171,6 +1039,48 @@ static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, doub
     }
     m->Nglobal = hd[0]; m->Dglobal = hd[1];
     m->phi_valid = true; m->phi_from_prev = false; m->gnext_valid = false; m->ll_pending = false; m->theta_valid = false;
+    return MMM_OK;
+}
+
+static int lda_create_impl(mmm_ctx* ctx, int D, int V, int K, double alpha, double eta, const int64_t* doc_ptr, const int32_t* term,
+                           const int32_t* count, const double* lambda0, int I, const int* J, const double* eta_i, const int32_t* features,
+                           mmm_lda** out, int R = 1)
+{
+    // 1. the arguments
+    if (!ctx) return MMM_ERR_ARG;
+    MMM_CHECK(ctx, out && doc_ptr && lambda0, "mmm_lda_create: NULL argument");
+    const bool ilda = I > 0;
+    IldaSpec il{I, J, eta_i, features, 0};
+    if (ilda) {
+        MMM_CHECK(ctx, J && eta_i && features, "mmm_ilda_create: NULL argument");
+        if (I > kIldaMaxI) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ilda_create: I=%d features (max %d)", I, kIldaMaxI);
+        for (int i = 0; i < I; ++i) { MMM_CHECK(ctx, J[i] >= 1, "mmm_ilda_create: J[%d] < 1", i); il.SJ += J[i]; }
+        if (il.SJ > kIldaMaxSJ) return mmm_fail(ctx, MMM_ERR_UNSUPPORTED, "mmm_ilda_create: sum(J)=%d (max %d)", il.SJ, kIldaMaxSJ);
+        for (int i = 0; i < I; ++i) for (int v = 0; v < V; ++v)
+            MMM_CHECK(ctx, features[(size_t)i * V + v] >= 0 && features[(size_t)i * V + v] < J[i], "mmm_ilda_create: feature value out of range (i=%d v=%d)", i, v);
+    }
+    MMM_CHECK(ctx, D >= 0 && V >= 1 && K >= 1, "mmm_lda_create: bad sizes D=%d V=%d K=%d", D, V, K);
+    *out = nullptr;
+    const int64_t nnz = doc_ptr[D];
+    const LdaRowShape shape = lda_row_shape(ctx->tune, D, V, K, nnz);      // the plan as far as the dimensions decide it, or the refusal of K
+    if (shape.refusal) return mmm_fail(ctx, shape.refusal, "%s", shape.why.c_str());      // (before the corpus is looked at)
+    if (int rc = mmm_check_csr(ctx, "mmm_lda_create", D, V, doc_ptr, term, count)) return rc;
+    // 2. the (term, count) pairs, and what the plan needs to know about the corpus
+    const std::vector<CountPair> tc = term_count_pairs(nnz, term, count);
+    const CorpusFacts facts = corpus_facts(D, V, doc_ptr, term, count, shape.scans_repeats());
+    // 3. every build and every launch geometry (mmm_geo_cus: the CU count the association of the cross-document sums is derived from)
+    const Planned<LdaPlan> planned = lda_plan(ctx->tune, mmm_geo_cus(ctx), R, D, V, K, shape, facts, ilda);
+    if (planned.refusal) return mmm_fail(ctx, planned.refusal, "%s", planned.why.c_str());
+
+    MMM_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<mmm_lda> guard(new mmm_lda());      // every early return below (MMM_HIP, ...) destroys the model and its buffers
+    mmm_lda* m = guard.get();
+    static_cast<LdaPlan&>(*m) = planned.plan;
+    m->tune = ctx->tune;
+    m->ctx = ctx; m->D = D; m->V = V; m->K = K; m->nnz = nnz; m->alpha = alpha; m->eta = eta;
+    m->R = R; m->rep_t.assign((size_t)R, 0); m->rep_hist.assign((size_t)R, 0);
+    if (int rc = lda_upload(m, doc_ptr, term, count, tc, lambda0, il)) return rc;      // 4.
+    if (int rc = lda_constructor_state(m)) return rc;                               // 5.
     *out = guard.release();
     mmm_ctx_model_created(ctx);
     return MMM_OK;

@@ -728,6 +728,55 @@ int mmm_extract_signatures(mmm_ctx* ctx, int D, int F, int J, int V, const int64
                            double* w /* [R][D][K] or NULL */, double* ll /* [R] */, double* ll_doc, double* unexplained /* [R][D] or NULL */,
                            int32_t* iters /* [R] */);
 
+/* ---- groups of samples: consensus k-means (Monti et al. 2003) of D samples on P features, B subsampled replicates for each of nk candidate
+ * numbers of groups in one call, then the pair counts and the inputs of PAC, the proportion of ambiguously clustered pairs (no counterpart in
+ * the reference).  x [D][P]: a sample's features, already transformed by the caller.  ks [nk]: the numbers of groups.
+ * Subsample of replicate b (GLOBAL index b0 + b).  keep == 0: every sample is a member.  Otherwise sample d is a member iff w < keep, w being
+ *   output word d % 4 of the Philox4x32-10 block with the constants and the key (seed low 32 bits, seed high 32 bits) of mmm_resample_counts
+ *   and the counter (d / 4, 0xC0000000, b0 + b, stream).  The members in ascending d are a = 0 .. n-1; the same subsample serves every k of the
+ *   replicate.  Bit 30 of the second counter word is set by no other user of these words: mmm_extract_signatures uses 0x80000000 | j with
+ *   j < 32, all others an index below 2^31 -- a subsample or a start shares no random word with any of them, whatever the stream.
+ * Distance.  dist(x, m) = sum_p (x_p - m_p)^2, p ascending from 0.0; each difference, product and sum is rounded separately.
+ * Start of the pair (b, k): k-means++ by integer thresholds.  u_i, i < k, is output word i % 4 of the block with the counter
+ *   (i / 4, 0xC0000000 | k, b0 + b, stream).  Centre 0 is member floor(u_0 n / 2^32); md_a = dist(x_a, centre 0).  For i = 1 .. k-1: cum_a = the
+ *   inclusive sum of md over a ascending, strictly sequential from 0.0; S = cum_{n-1}.  S > 0: T_a = floor((cum_a / S) * 2^32) (an IEEE division;
+ *   the product is exact), and centre i is the first member a with T_a > u_i -- it exists because T_{n-1} = 2^32, and it is never a member with
+ *   md_a = 0, whose T_a = T_{a-1}.  S = 0 (every member coincides with a centre): centre i is the lowest a that is not yet the member of a
+ *   centre.  Then md_a = min(md_a, dist(x_a, centre i)).  A centre is a copy of its member's row.
+ *   n < k: the pair is SKIPPED -- its labels are all -1, iters 0, inertia 0.
+ * Iteration t = 1 .. maxiter.  Every member's label becomes the centre with the smallest dist, ties to the lowest centre.  If no label changed,
+ *   stop (in iteration 1 every label counts as changed).  Otherwise centre c becomes (the sum of its members' rows) / count_c, an IEEE division
+ *   per feature, the sum in the order of mmm_extract_signatures: sample d (its index in x, not a) belongs to stripe d mod 16; a stripe's sum runs
+ *   over its members of the centre in ascending d from 0.0; the 16 stripe sums are then added in ascending stripe order from 0.0.  A centre
+ *   without members keeps its value.  iters = the iterations run (the stopping one included); iters == maxiter: the pair did not settle.
+ *   inertia = the sum over the members of their smallest dist at the LAST assignment, in the same stripe order.
+ * Pair counts over the B replicates of THIS call (the counts of chunked calls add), integers: together[k][i][j] = the number of replicates b
+ *   in which i and j are both members and the pair (b, k) was not skipped (the diagonal: how often i was drawn in such a replicate);
+ *   same[k][i][j] = the number of those in which their labels are equal.  together is kept per k because the skipped pairs differ per k: so
+ *   0 <= same <= together holds entry by entry, same is symmetric, same[k][i][i] = together[k][i][i].
+ * PAC inputs, in 64-bit integers, over the pairs i < j: valid[k] = #{together > 0}; ambiguous[k] = #{1000 same > pac_lo together and
+ *   1000 same < pac_hi together} (per mille bounds of the consensus same / together).  The quotient ambiguous / valid is the caller's.
+ * Only +, -, x, /, comparisons and integers decide every output: the same arguments give the same bits on every run and under every launch
+ *   geometry (`waves`, `placement`, the number of pairs in flight).  Consequences.  (a) labels, iters and inertia of a call with (b0, B) are a
+ *   slice of the call with (0, b0 + B).  (b) together and same are additive: counts(0, B1 + B2) = counts(0, B1) + counts(B1, B2); valid and
+ *   ambiguous of the whole follow from the summed counts by the rule above.
+ * Outputs: labels [nk][B][D] int8, -1 = not a member or skipped; iters, inertia [nk][B]; together, same [nk][D][D] uint32, ambiguous, valid [nk]
+ *   int64, each of the four may be NULL (all four NULL: the pair pass does not run).
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, 8; else 1, 2, 4, 8 or 16).  placement: 0 = the library's
+ *   choice -- the members' rows, md, cum, the labels, the member lists and the 16 stripe slabs of the centre sums are held in LDS when
+ *   8 (kmax P + 16) + 2328 + 8 (2 D + 16 kmax P + D (P | 1)) + 12 D bytes do not exceed 160 KiB (kmax = the largest k), and in a per-block
+ *   workspace in memory otherwise; 1 = in LDS where they fit (the same as 0); 2 = in memory.
+ * Limits: 1 <= D <= 4096, 1 <= P <= 256, 1 <= nk <= 16, 1 <= k <= 32, nk B D < 2^31, b0 + B <= 2^31 - 1.  Every entry of x is finite with
+ *   |x| <= 1e150, which keeps every square and every sum of the definition finite.
+ * MMM_ERR_ARG, nothing written: NULL pointers (ctx, x, ks; labels, iters, inertia with B > 0), D < 1, P < 1, nk < 1, a k < 1, B < 0, b0 < 0,
+ *   b0 + B > 2^31 - 1, maxiter < 1, not 0 <= pac_lo < pac_hi <= 1000, waves not one of 0, 1, 2, 4, 8, 16, placement not 0, 1 or 2, an entry of x
+ *   that is not finite or beyond 1e150.  MMM_ERR_UNSUPPORTED, with the limit in the message: D > 4096, P > 256, nk > 16, a k > 32,
+ *   nk B D >= 2^31.  B = 0: MMM_OK, nothing written.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_cluster_samples(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, int nk, const int32_t* ks /* [nk] */, int B, int b0, uint32_t keep,
+                        uint64_t seed, uint32_t stream, int maxiter, int pac_lo, int pac_hi, int waves, int placement, int8_t* labels /* [nk][B][D] */,
+                        int32_t* iters, double* inertia /* [nk][B] */, uint32_t* together, uint32_t* same /* [nk][D][D] or NULL */,
+                        int64_t* ambiguous, int64_t* valid /* [nk] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

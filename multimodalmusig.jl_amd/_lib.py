@@ -155,6 +155,8 @@ _SIGS = {
     "mmm_signature_decompose": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_extract_signatures": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int,
                                          C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "mmm_cluster_samples": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 

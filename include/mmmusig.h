@@ -777,6 +777,47 @@ int mmm_cluster_samples(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */
                         int32_t* iters, double* inertia /* [nk][B] */, uint32_t* together, uint32_t* same /* [nk][D][D] or NULL */,
                         int64_t* ambiguous, int64_t* valid /* [nk] or NULL */);
 
+/* ---- exposures against sample covariates: rank statistics of P features against C covariates over D samples, with B permutations of the
+ * covariate rows (within strata) for exact p-values under ties and Westfall-Young max-T adjustment (no counterpart in the reference;
+ * DESIGN.md section 4.19).  x [D][P]: a sample's features.  y [D][C]: its covariates.  levels [C]: 0 = covariate c is numeric and owns one
+ * column; G >= 1 = categorical, y[d][c] is an integral code in 0 .. G-1 and the covariate owns G indicator columns.  Q = the sum of the
+ * column counts; the columns stand in covariate order.
+ * Doubled midranks.  For n values v: r2_d = 2 #{e : v_e < v_d} + #{e : v_e = v_d} + 1, the comparisons IEEE (-0.0 equals 0.0): integers in
+ *   2 .. 2n whose sum is n (n + 1), whose mean is exactly n + 1.  Rx[d][p] = r2 of feature p over all D samples.  Y[d][q] = r2 of the covariate
+ *   for a numeric column; for the indicator column of level g, 1 if the code is g, else 0.  Both fit 16 bits; the library forms them on the host.
+ * Weights, integers all.  SSx_p = sum_d (Rx[d][p] - (D + 1))^2.  w_q = sum_d (Y[d][q] - (D + 1))^2 for a numeric column, n_g (the number of
+ *   samples with code g) for an indicator column.
+ * Permutation of replicate b (GLOBAL index b0 + b).  key_d = output word d % 4 of the Philox4x32-10 block with the constants and the key
+ *   (seed low 32 bits, seed high 32 bits) of mmm_resample_counts and the counter (d / 4, 0xE0000000, b0 + b, stream).  Bits 31, 30 and 29 of
+ *   the second counter word together are set by no other user of these words: mmm_extract_signatures uses 0x80000000 | j with j < 32,
+ *   mmm_cluster_samples 0xC0000000 | k with k <= 32, all others (the resampler, the split, the simulator) an index below 2^31 -- a
+ *   permutation shares no random word with any of them, whatever the stream.  s_d = strata[d], or 0 without strata.  slot_0 .. slot_{D-1}
+ *   are the samples in ascending (s_d, d); e_0 .. e_{D-1} the samples in ascending (s_d, key_d, d); pi(slot_j) = e_j.  Both lists carry the
+ *   same sequence of strata, so pi maps every stratum onto itself.  Equal keys are ordered by d: the orders of a stratum are not exactly
+ *   equally likely, the bias is below D^2 / 2^33 (the chance that two of D keys coincide) and is accepted.
+ * Statistic.  Z_b[p][q] = sum_i Rx[i][p] Y[pi(i)][q]: sample i keeps its features and receives the covariate row of pi(i); an integer.
+ *   Zc = Z_b[p][q] - (D + 1) sum_d Y[d][q]; |Zc| <= 2^38 at D = 4096.  t_b[p][c] = (the sum over the columns q of c, ascending, from 0.0,
+ *   skipping w_q = 0, of ((double)Zc (double)Zc) / (double)w_q) / (double)SSx_p; the product, every division and every sum is rounded
+ *   separately; t = 0 when SSx_p = 0 (a constant feature).  (D - 1) t is the tie-corrected Kruskal-Wallis H of a categorical covariate (with
+ *   two levels the squared Wilcoxon rank-sum z) and (D - 1) rho^2, rho Spearman's coefficient, of a numeric one; the scaling is the caller's.
+ * Outputs.  obs [P][C] and zc_obs [P][Q] (or NULL): t and Zc under the identity permutation, formed by the same device code.
+ *   ge[p][c] = #{b in this call : t_b[p][c] >= obs[p][c]}.  M_b[c] = max_p t_b[p][c], within a covariate only: statistics of covariates with
+ *   different numbers of levels are not on one scale.  ge_max[p][c] = #{b : M_b[c] >= obs[p][c]}.  maxstat [B][C] (or NULL) = M_b[c].
+ * Everything the device sums is an integer; t is formed by one thread in the written order, maxima and comparisons are exact.
+ *   Consequences.  (a) Every output is the same bits on every run and under every `waves`.  (b) maxstat of a call with (b0, B) is a slice of
+ *   the call with (0, b0 + B).  (c) ge and ge_max of chunked calls add.  (d) obs and zc_obs do not depend on B, b0, seed or stream.
+ *   (e) If every stratum has one member, every pi is the identity, t_b = obs and ge = ge_max = B everywhere (a maximum is no smaller than any obs).
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, 4; else 1, 2, 4, 8 or 16).
+ * Limits: 1 <= D <= 4096, 1 <= P <= 256, 1 <= C, Q <= 256, b0 + B <= 2^31 - 1, 0 <= strata[d] < D.
+ * MMM_ERR_ARG, nothing written: NULL pointers (ctx, x, levels, y, obs; ge and ge_max with B > 0), D < 1, P < 1, C < 1, a negative level,
+ *   B < 0, b0 < 0, b0 + B > 2^31 - 1, an x or y that is not finite, a categorical y that is not an integer in 0 .. G-1, a stratum out of range,
+ *   waves not one of 0, 1, 2, 4, 8, 16.  MMM_ERR_UNSUPPORTED, with the limit in the message: D > 4096, P > 256, Q > 256.  B = 0: obs and
+ *   zc_obs are written, the counts are untouched, MMM_OK.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, int C, const int32_t* levels /* [C] */,
+                            const double* y /* [D][C] */, const int32_t* strata /* [D] or NULL */, int B, int b0, uint64_t seed, uint32_t stream,
+                            int waves, double* obs /* [P][C] */, int64_t* zc_obs /* [P][Q] or NULL */, uint32_t* ge, uint32_t* ge_max /* [P][C] */,
+                            double* maxstat /* [B][C] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

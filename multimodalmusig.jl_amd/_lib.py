@@ -157,6 +157,8 @@ _SIGS = {
                                          C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]),
     "mmm_cluster_samples": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_associate_exposures": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, vp, vp, vp, vp,
+                                          vp]),
 }
 
 

@@ -790,8 +790,8 @@ int mmm_cluster_samples(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */
  * Permutation of replicate b (GLOBAL index b0 + b).  key_d = output word d % 4 of the Philox4x32-10 block with the constants and the key
  *   (seed low 32 bits, seed high 32 bits) of mmm_resample_counts and the counter (d / 4, 0xE0000000, b0 + b, stream).  Bits 31, 30 and 29 of
  *   the second counter word together are set by no other user of these words: mmm_extract_signatures uses 0x80000000 | j with j < 32,
- *   mmm_cluster_samples 0xC0000000 | k with k <= 32, all others (the resampler, the split, the simulator) an index below 2^31 -- a
- *   permutation shares no random word with any of them, whatever the stream.  s_d = strata[d], or 0 without strata.  slot_0 .. slot_{D-1}
+ *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association 0xA0000000 (bit 30 clear), all others (the resampler, the
+ *   split, the simulator) an index below 2^31 -- a permutation shares no random word with any of them, whatever the stream.  s_d = strata[d], or 0 without strata.  slot_0 .. slot_{D-1}
  *   are the samples in ascending (s_d, d); e_0 .. e_{D-1} the samples in ascending (s_d, key_d, d); pi(slot_j) = e_j.  Both lists carry the
  *   same sequence of strata, so pi maps every stratum onto itself.  Equal keys are ordered by d: the orders of a stratum are not exactly
  *   equally likely, the bias is below D^2 / 2^33 (the chance that two of D keys coincide) and is accepted.
@@ -817,6 +817,65 @@ int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P
                             const double* y /* [D][C] */, const int32_t* strata /* [D] or NULL */, int B, int b0, uint64_t seed, uint32_t stream,
                             int waves, double* obs /* [P][C] */, int64_t* zc_obs /* [P][Q] or NULL */, uint32_t* ge, uint32_t* ge_max /* [P][C] */,
                             double* maxstat /* [B][C] or NULL */);
+
+/* ---- exposures against survival: permutation tests of P features and C group covariates against a right-censored time-to-event outcome
+ * over D samples, B permutations of the outcome rows (within strata): the log-rank test of every group covariate, the Cox score (trend) test
+ * of every ranked feature with max-T adjustment over the features, and the maximally selected log-rank statistic over every cutpoint of a
+ * feature, its p-value corrected for the scan by permuting the whole scan (no counterpart in the reference).
+ * x [D][P]: a sample's features.  groups [D][C]: its codes, groups[d][c] in 0 .. levels[c]-1 (NULL iff C == 0); Q = the sum of the levels.
+ * time [D] >= 0, event [D] in {0, 1} (1 = the event was seen at time, 0 = censored there).  strata [D] or NULL.
+ * Strata.  s_d = strata[d], or 0 without strata.  A stratum is a code with at least one member; n_s its size.
+ * Scores, per stratum s.  u_1 < u_2 < .. are the distinct times of the stratum's events (IEEE comparisons), d_j = #{i in s : event_i = 1,
+ *   time_i = u_j}, n_j = #{i in s : time_i >= u_j}.  H_i = the sum over the j with u_j <= time_i, ascending, from 0.0, of (double)d_j /
+ *   (double)n_j, every quotient and every sum rounded separately (the Nelson-Aalen estimate at time_i).  a_i = (double)event_i - H_i, the
+ *   log-rank (Savage) score.  A_i = rint(a_i 2^24), ties to even, an int32: H < 1 + ln 4096 < 9.4, so |A_i| < 2^27.3.  Any fixed score
+ *   vector gives a valid permutation test, so the quantisation costs nothing statistically, and every sum below is an exact integer.
+ * Features.  Rx[d][p] = the doubled midranks of mmm_associate_exposures (2 #{less} + #{equal} + 1 over all D samples; 16 bits).  o_p = the
+ *   samples in ascending (x[.][p], d), the comparisons IEEE (-0.0 equals 0.0).
+ * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
+ *   second Philox counter word 0xA0000000: bits 31 and 29 without bit 30 are set by no other user of these words (mmm_extract_signatures
+ *   uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_associate_exposures 0xE0000000, all others an index
+ *   below 2^31).  Sample i keeps its features and groups and receives the score of pi(i): Api_i = A[pi(i)].
+ * One rule for every test column, an integer column f over the samples.  T_b(f) = sum_i f_i Api_i, an integer.  With F_s = the sum of f over
+ *   stratum s and SA_s = the sum of A over it: E(f) = the sum over the strata, in ascending code, from 0.0, of ((double)F_s (double)SA_s) /
+ *   (double)n_s.  With NF_s = n_s sum f^2 - F_s^2 and NA_s = n_s sum A^2 - SA_s^2, formed exactly as integers (NA_s needs 128 bits) and
+ *   converted to double by round-to-nearest-even: V(f) = the sum over the strata with n_s >= 2, in ascending code, from 0.0, of
+ *   ((double)NF_s (double)NA_s) / (((double)n_s (double)n_s) (double)(n_s - 1)).  Every product, division and sum is rounded separately.
+ *   t_b(f): dz = (double)T_b - E, t = (dz dz) / V; where V is not > 0, t is 0 and the column is skipped in sums and maxima.  |T| < 2^53 in
+ *   every family (Rx <= 2^13, D <= 2^12, |A| < 2^27.3): the conversion is exact.  E and V are the exact mean and variance of T under the
+ *   within-stratum permutation; the host forms them once per call.
+ * Trend.  f = Rx[.][p]: the Cox score test on the ranked feature in its permutation form.  z_trend[p] = T under the identity.
+ * Group.  t_b[c] = the sum over the levels g of covariate c, ascending, from 0.0, of t_b(the indicator of code g).  u_group[q] = T of the
+ *   indicator under the identity = 2^24 (O_g - E_g), observed minus expected events of the level.  With two levels and no strata t / 2 is
+ *   the log-rank chi-square with the permutation variance; with more levels t is the sum of the one-against-rest statistics.
+ * Cut.  On iff m_lo >= 1.  For j = 1 .. D-1, f_j = the indicator of {o_p(0) .. o_p(j-1)}.  Cut j is allowed iff x[o_p(j-1)][p] <
+ *   x[o_p(j)][p] and m_lo <= j <= D - m_lo.  t_b^cut[p] = the maximum over the allowed j with V(f_j) > 0 of t_b(f_j), 0 if there is none.
+ *   cut_at[p] = the lowest such j that attains the maximum under the identity, 0 if there is none: x > x[o_p(cut_at - 1)][p] is "high".
+ * Outputs.  obs_trend [P], obs_group [C], obs_cut [P]: the statistics under the identity, formed by the same device code (a launch of one
+ *   block with pi = the identity), as are z_trend [P] (or NULL), u_group [Q] (or NULL) and cut_at [P].  Every ge.. = #{b in this call : t_b >=
+ *   obs}: ge_trend [P], ge_cut [P], ge_group [C].  M_b^trend = max_p t_b^trend[p], M_b^cut = max_p t_b^cut[p] (0 with the cuts off);
+ *   gemax_trend[p] = #{b : M_b^trend >= obs_trend[p]}, gemax_cut likewise.  maxstat [B][2] (or NULL) = (M_b^trend, M_b^cut).  A group
+ *   covariate has one statistic and gets ge only.  With m_lo = 0 obs_cut, cut_at, ge_cut and gemax_cut may be NULL and are not written.
+ * Consequences.  (a) Every output is the same bits on every run and under every `waves`.  (b) maxstat of a call with (b0, B) is a slice of
+ *   the call with (0, b0 + B).  (c) The counts of chunked calls add.  (d) Every obs.., z_trend, u_group and cut_at is independent of B, b0,
+ *   seed and stream.  (e) If every stratum has one member, every V is 0, every statistic is 0 and every count equals B.  (f) Without events
+ *   every A_i is 0, every V is 0, and (e) holds as well.
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, 4; else 1, 2, 4, 8 or 16).
+ * Limits: 1 <= D <= 4096, 1 <= P <= 256, 0 <= C, levels >= 1, Q <= 256, at most 64 distinct strata (the host's per-cut constants cost
+ *   O(P D 64)), 0 <= strata[d] < D, b0 + B <= 2^31 - 1, 0 <= m_lo <= max(1, D / 2) (m_lo = 1 is accepted at every D; D = 1 has no cut).
+ * MMM_ERR_ARG, nothing written: NULL pointers (ctx, x, time, event, obs_trend; levels, groups, obs_group with C > 0; obs_cut, cut_at with
+ *   m_lo >= 1; the counts of the families that are on with B > 0), D < 1, P < 1, C < 0, a level < 1, B < 0, b0 < 0, b0 + B > 2^31 - 1, m_lo
+ *   out of range, an x that is not finite, a time that is not finite or is negative, an event other than 0 or 1, a code outside 0 .. G-1, a
+ *   stratum outside 0 .. D-1, waves not one of 0, 1, 2, 4, 8, 16.  MMM_ERR_UNSUPPORTED, with the limit in the message: D > 4096, P > 256,
+ *   Q > 256, more than 64 distinct strata.  B = 0: the obs.. outputs are written, the counts and maxstat are untouched, MMM_OK.  Every
+ *   argument is checked before a device is asked for.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_survival_association(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, int C, const int32_t* levels /* [C] */,
+                             const int32_t* groups /* [D][C] or NULL */, const double* time /* [D] */, const uint8_t* event /* [D] */,
+                             const int32_t* strata /* [D] or NULL */, int m_lo, int B, int b0, uint64_t seed, uint32_t stream, int waves,
+                             double* obs_trend /* [P] */, int64_t* z_trend /* [P] or NULL */, double* obs_group /* [C] */,
+                             int64_t* u_group /* [Q] or NULL */, double* obs_cut /* [P] */, int32_t* cut_at /* [P] */, uint32_t* ge_trend,
+                             uint32_t* gemax_trend, uint32_t* ge_cut, uint32_t* gemax_cut /* [P] each */, uint32_t* ge_group /* [C] */,
+                             double* maxstat /* [B][2] or NULL */);
 
 #ifdef __cplusplus
 }

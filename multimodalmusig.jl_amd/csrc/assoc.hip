@@ -15,11 +15,9 @@
 //            block in LDS first was measured: no gain at 560 x 10 x 3, and its 32 KiB cost a block per CU at 4096 x 64 x 64).
 // The identity permutation (obs, zc_obs) is a launch of one block of the same kernel with pi[d] = d.
 #include "mmm_internal.h"
-#include "mmm_philox.h"
+#include "mmm_perm.h"
 
-#include <algorithm>
 #include <cmath>
-#include <vector>
 
 namespace {
 
@@ -95,25 +93,7 @@ __global__ __launch_bounds__(1024) void k_assoc(const AsArgs a)
             b = ctl[0];
             if (b >= a.B) break;
             // ---- sort
-            for (int i4 = tid; 4 * i4 < n2; i4 += nt) {
-                uint32_t u[4];
-                philox4x32_10((uint32_t)i4, kAsBits, (uint32_t)(a.b0 + b), a.stream, a.k0, a.k1, u);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int d = 4 * i4 + j;
-                    if (d < n2) keys[d] = d < D ? ((unsigned long long)a.strat[d] << 44) | ((unsigned long long)u[j] << 12) | (unsigned long long)d : ~0ull;
-                }
-            }
-            __syncthreads();
-            for (int k = 2; k <= n2; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int t = tid; t < (n2 >> 1); t += nt) {
-                        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-                        const unsigned long long ka = keys[i], kb = keys[l];
-                        if ((ka > kb) == ((i & k) == 0)) { keys[i] = kb; keys[l] = ka; }
-                    }
-                    __syncthreads();
-                }
+            perm_sorted_keys(keys, tid, nt, D, n2, a.strat, kAsBits, (uint32_t)(a.b0 + b), a.stream, a.k0, a.k1);
             for (int j = tid; j < D; j += nt) pi[a.slot[j]] = (uint16_t)(keys[j] & 0xFFFull);
         } else {
             for (int d = tid; d < D; d += nt) pi[d] = (uint16_t)d;
@@ -200,19 +180,6 @@ __global__ __launch_bounds__(1024) void k_assoc(const AsArgs a)
     }
 }
 
-// doubled midranks of v[0], v[stride], ..: 2 #{less} + #{equal} + 1 (IEEE comparisons: -0.0 equals 0.0)
-void as_ranks(const double* v, size_t stride, int n, std::vector<int>& idx, uint16_t* out, size_t ostride)
-{
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.begin() + n, [&](int i, int j) { return v[(size_t)i * stride] < v[(size_t)j * stride]; });
-    for (int lo = 0; lo < n;) {
-        int hi = lo + 1;
-        while (hi < n && v[(size_t)idx[hi] * stride] == v[(size_t)idx[lo] * stride]) ++hi;
-        for (int j = lo; j < hi; ++j) out[(size_t)idx[j] * ostride] = (uint16_t)(2 * lo + (hi - lo) + 1);
-        lo = hi;
-    }
-}
-
 } // namespace
 
 extern "C" int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double* x, int C, const int32_t* levels, const double* y, const int32_t* strata, int B,
@@ -251,7 +218,7 @@ extern "C" int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double*
     std::vector<long long> ssx((size_t)P, 0), w((size_t)Q, 0), cen((size_t)Q, 0);
     std::vector<int> col0((size_t)C + 1), idx((size_t)D);
     for (int p = 0; p < P; ++p) {
-        as_ranks(x + p, (size_t)P, D, idx, rxt.data() + (size_t)p * D, 1);
+        perm_ranks(x + p, (size_t)P, D, idx, rxt.data() + (size_t)p * D, 1);
         for (int d = 0; d < D; ++d) {
             const long long dv = (long long)rxt[(size_t)p * D + d] - (D + 1);
             ssx[p] += dv * dv;
@@ -261,7 +228,7 @@ extern "C" int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double*
     for (int c = 0; c < C; ++c) {
         col0[c] = q0;
         if (levels[c] == 0) {
-            as_ranks(y + c, (size_t)C, D, idx, yq.data() + q0, (size_t)Qs);
+            perm_ranks(y + c, (size_t)C, D, idx, yq.data() + q0, (size_t)Qs);
             for (int d = 0; d < D; ++d) {
                 const long long dv = (long long)yq[(size_t)d * Qs + q0] - (D + 1);
                 w[q0] += dv * dv;

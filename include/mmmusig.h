@@ -790,7 +790,8 @@ int mmm_cluster_samples(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */
  * Permutation of replicate b (GLOBAL index b0 + b).  key_d = output word d % 4 of the Philox4x32-10 block with the constants and the key
  *   (seed low 32 bits, seed high 32 bits) of mmm_resample_counts and the counter (d / 4, 0xE0000000, b0 + b, stream).  Bits 31, 30 and 29 of
  *   the second counter word together are set by no other user of these words: mmm_extract_signatures uses 0x80000000 | j with j < 32,
- *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association 0xA0000000 (bit 30 clear), all others (the resampler, the
+ *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association 0xA0000000 (bit 30 clear), mmm_classify_exposures 0x90000000
+ *   (bits 30 and 29 clear, bit 28 set), all others (the resampler, the
  *   split, the simulator) an index below 2^31 -- a permutation shares no random word with any of them, whatever the stream.  s_d = strata[d], or 0 without strata.  slot_0 .. slot_{D-1}
  *   are the samples in ascending (s_d, d); e_0 .. e_{D-1} the samples in ascending (s_d, key_d, d); pi(slot_j) = e_j.  Both lists carry the
  *   same sequence of strata, so pi maps every stratum onto itself.  Equal keys are ordered by d: the orders of a stratum are not exactly
@@ -834,7 +835,8 @@ int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P
  *   samples in ascending (x[.][p], d), the comparisons IEEE (-0.0 equals 0.0).
  * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
  *   second Philox counter word 0xA0000000: bits 31 and 29 without bit 30 are set by no other user of these words (mmm_extract_signatures
- *   uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_associate_exposures 0xE0000000, all others an index
+ *   uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_associate_exposures 0xE0000000,
+ *   mmm_classify_exposures 0x90000000, all others an index
  *   below 2^31).  Sample i keeps its features and groups and receives the score of pi(i): Api_i = A[pi(i)].
  * One rule for every test column, an integer column f over the samples.  T_b(f) = sum_i f_i Api_i, an integer.  With F_s = the sum of f over
  *   stratum s and SA_s = the sum of A over it: E(f) = the sum over the strata, in ascending code, from 0.0, of ((double)F_s (double)SA_s) /
@@ -876,6 +878,58 @@ int mmm_survival_association(mmm_ctx* ctx, int D, int P, const double* x /* [D][
                              int64_t* u_group /* [Q] or NULL */, double* obs_cut /* [P] */, int32_t* cut_at /* [P] */, uint32_t* ge_trend,
                              uint32_t* gemax_trend, uint32_t* ge_cut, uint32_t* gemax_cut /* [P] each */, uint32_t* ge_group /* [C] */,
                              double* maxstat /* [B][2] or NULL */);
+
+/* ---- a binary label against the exposures together: the cross-validated AUC of a ridge-penalised logistic regression of y on P features
+ * over D samples, for L penalties, with B permutations of the feature rows (within strata); the maximum over the penalties is permuted with
+ * the rest, so the p-value of the best penalty covers its choice (no counterpart in the reference).
+ * x [D][P]: a sample's features, as given (the Python layer standardises them).  y [D] in {0, 1}.  strata [D] or NULL.  fold [R][D]: the fold
+ * (< F) of sample i in repeat r, formed by the caller.  lambda [L], each > 0 and finite.  Q = P + 1 coefficients, the intercept first.
+ * n_1 = #{y = 1}, n_0 = #{y = 0}.
+ * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
+ *   second Philox counter word 0x90000000: bits 31 and 28 without bits 30 and 29 are set by no other user of these words
+ *   (mmm_extract_signatures uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association
+ *   0xA0000000, mmm_associate_exposures 0xE0000000, all others an index below 2^31).  Sample i keeps its label, its folds and its stratum
+ *   and receives the feature row x[pi(i)].  The identity replicate uses pi = id.
+ * One fit (T, lam), T a set of samples.  z_i = (1, x[pi(i)][0 .. P-1]), pen = (0, lam, .., lam).  From w = 0, for it = 1, 2, ..:
+ *   eta_i = w_0 + sum_{j = 1 .. P} z_ij w_j, in ascending j, starting from w_0.  ec_i = -700 if eta_i < -700, 700 if eta_i > 700, else eta_i
+ *   (a NaN stays).  p_i = 1 / (1 + ar_exp(-ec_i)), ar_exp of csrc/mmm_arith.h: the clamp keeps every operand of the quotient normal and
+ *   finite.  om_i = p_i (1 - p_i), r_i = p_i - (double)y_i.
+ *   g_j = (sum_{i in T} r_i z_ij) + pen_j w_j.  H_jk = (sum_{i in T} z_ij (om_i z_ik)) + [j = k] pen_j, for j >= k (nothing is added off the
+ *   diagonal).  Both sums over i run in the stripe order of mmm_extract_signatures: sample i belongs to stripe i mod 16; a stripe's sum runs
+ *   over its members of T in ascending i from 0.0; the 16 stripe sums are then added in ascending stripe order from 0.0.  Every product and
+ *   every sum is rounded separately (no contraction).
+ *   H = C C' by Cholesky in column order: C_kk = sqrt(H_kk - sum_{m < k} C_km C_km), C_jk = (H_jk - sum_{m < k} C_jm C_km) / C_kk, the
+ *   subtractions one by one in ascending m.  If a radicand is not > 0 or not finite, the fit ends with status 2 and w is what it was before
+ *   this iteration.  Otherwise C u = g forward (u_k = (g_k - sum_{m < k} C_km u_m) / C_kk, ascending m), C' d = u backward (d_k = (u_k -
+ *   sum_{m > k} C_mk d_m) / C_kk, descending m), w <- w - d.  If a w_j is not finite the fit ends with status 2 (with that w); else if
+ *   max_j |d_j| <= tol, with status 0; else if it = maxiter, with status 1.  Division and square root are the IEEE correctly rounded ones.
+ * Scores and statistic.  For (b, r, l) and every fold f: fit (T = {i : fold[r][i] != f}, lambda[l]); s_i = eta_i (unclamped) under the final
+ *   w for every i with fold[r][i] = f.  U2(b, r, l) = sum_{i : y = 1} sum_{j : y = 0} (2 [s_i > s_j] + [s_i = s_j]), a NaN comparing false.
+ *   S_b[l] = sum_r U2(b, r, l): the cross-validated AUC is S / (2 R n_1 n_0).  M_b = max_l S_b[l].  Integers all: every comparison between
+ *   replicates is exact once the scores are.
+ * Outputs.  Under the identity, by a launch of one block of the same device code: scores [R][L][D] (or NULL), u2_obs [R][L] (or NULL),
+ *   s_obs [L], and coef [L][Q] with full_iters [L][2] = (iterations, status) (or NULL each) of the fit on T = all samples per penalty.
+ *   ge[l] = #{b in this call : S_b[l] >= s_obs[l]}, gemax[l] = #{b : M_b >= s_obs[l]}, maxstat [B] (or NULL) = M_b.  events [4] = the fits
+ *   that ended with status 1 and with status 2 under the identity (the all-sample fits included), then among the permutations of this call:
+ *   counted, not raised -- any deterministic procedure gives a valid permutation test, a fit that stops at maxiter costs only power.
+ * Consequences.  (a) Every output is the same bits on every run and under every `waves`.  (b) maxstat of a call with (b0, B) is a slice of
+ *   the call with (0, b0 + B).  (c) ge, gemax and events[2], events[3] of chunked calls add.  (d) scores, u2_obs, s_obs, coef, full_iters,
+ *   events[0] and events[1] are independent of B, b0, seed and stream.
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, 4; else 1, 2, 4, 8 or 16).  The permuted rows are
+ *   held in LDS when the block then stays within 64 KiB, and read through pi from memory otherwise; no bit depends on it.
+ * Limits: 2 <= D <= 4096, 1 <= P <= 63, 2 <= F <= 255, 1 <= R <= 64, 1 <= L <= 32, 0 <= strata[d] < D, b0 + B <= 2^31 - 1.
+ * MMM_ERR_ARG, nothing written and before any launch: NULL pointers (ctx, x, y, fold, lambda, s_obs, events; ge and gemax with B > 0), D < 2,
+ *   P < 1, R < 1, F < 2, L < 1, B < 0, b0 < 0, b0 + B > 2^31 - 1, maxiter < 1, not tol >= 0, a lambda that is not > 0 and finite, an x that
+ *   is not finite, a y other than 0 or 1, a fold >= F, a stratum outside 0 .. D-1, waves not one of 0, 1, 2, 4, 8, 16, a class without
+ *   members, a training set (r, f) that lacks a class.  MMM_ERR_UNSUPPORTED, with the limit in the message: D > 4096, P > 63, R > 64,
+ *   F > 255, L > 32.  B = 0: the identity outputs and events are written, ge, gemax and maxstat are untouched, MMM_OK.  No collective: on a
+ *   multi-rank context it acts on its arrays. */
+int mmm_classify_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, const uint8_t* y /* [D] */,
+                           const int32_t* strata /* [D] or NULL */, int R, int F, const uint8_t* fold /* [R][D] */, int L,
+                           const double* lambda /* [L] */, int maxiter, double tol, int B, int b0, uint64_t seed, uint32_t stream, int waves,
+                           double* scores /* [R][L][D] or NULL */, int64_t* u2_obs /* [R][L] or NULL */, int64_t* s_obs /* [L] */,
+                           double* coef /* [L][Q] or NULL */, int32_t* full_iters /* [L][2] or NULL */, uint32_t* ge, uint32_t* gemax /* [L] each */,
+                           int64_t* maxstat /* [B] or NULL */, uint32_t* events /* [4] */);
 
 #ifdef __cplusplus
 }

@@ -791,7 +791,7 @@ int mmm_cluster_samples(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */
  *   (seed low 32 bits, seed high 32 bits) of mmm_resample_counts and the counter (d / 4, 0xE0000000, b0 + b, stream).  Bits 31, 30 and 29 of
  *   the second counter word together are set by no other user of these words: mmm_extract_signatures uses 0x80000000 | j with j < 32,
  *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association 0xA0000000 (bit 30 clear), mmm_classify_exposures 0x90000000
- *   (bits 30 and 29 clear, bit 28 set), all others (the resampler, the
+ *   (bits 30 and 29 clear, bit 28 set), mmm_cox_exposures 0xB0000000 (bit 30 clear), all others (the resampler, the
  *   split, the simulator) an index below 2^31 -- a permutation shares no random word with any of them, whatever the stream.  s_d = strata[d], or 0 without strata.  slot_0 .. slot_{D-1}
  *   are the samples in ascending (s_d, d); e_0 .. e_{D-1} the samples in ascending (s_d, key_d, d); pi(slot_j) = e_j.  Both lists carry the
  *   same sequence of strata, so pi maps every stratum onto itself.  Equal keys are ordered by d: the orders of a stratum are not exactly
@@ -834,9 +834,9 @@ int mmm_associate_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P
  * Features.  Rx[d][p] = the doubled midranks of mmm_associate_exposures (2 #{less} + #{equal} + 1 over all D samples; 16 bits).  o_p = the
  *   samples in ascending (x[.][p], d), the comparisons IEEE (-0.0 equals 0.0).
  * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
- *   second Philox counter word 0xA0000000: bits 31 and 29 without bit 30 are set by no other user of these words (mmm_extract_signatures
+ *   second Philox counter word 0xA0000000: bits 31 and 29 without bits 30 and 28 are set by no other user of these words (mmm_extract_signatures
  *   uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_associate_exposures 0xE0000000,
- *   mmm_classify_exposures 0x90000000, all others an index
+ *   mmm_classify_exposures 0x90000000, mmm_cox_exposures 0xB0000000 (bit 28 set as well), all others an index
  *   below 2^31).  Sample i keeps its features and groups and receives the score of pi(i): Api_i = A[pi(i)].
  * One rule for every test column, an integer column f over the samples.  T_b(f) = sum_i f_i Api_i, an integer.  With F_s = the sum of f over
  *   stratum s and SA_s = the sum of A over it: E(f) = the sum over the strata, in ascending code, from 0.0, of ((double)F_s (double)SA_s) /
@@ -888,7 +888,7 @@ int mmm_survival_association(mmm_ctx* ctx, int D, int P, const double* x /* [D][
  * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
  *   second Philox counter word 0x90000000: bits 31 and 28 without bits 30 and 29 are set by no other user of these words
  *   (mmm_extract_signatures uses 0x80000000 | j with j < 32, mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_survival_association
- *   0xA0000000, mmm_associate_exposures 0xE0000000, all others an index below 2^31).  Sample i keeps its label, its folds and its stratum
+ *   0xA0000000, mmm_cox_exposures 0xB0000000 (bit 29 set as well), mmm_associate_exposures 0xE0000000, all others an index below 2^31).  Sample i keeps its label, its folds and its stratum
  *   and receives the feature row x[pi(i)].  The identity replicate uses pi = id.
  * One fit (T, lam), T a set of samples.  z_i = (1, x[pi(i)][0 .. P-1]), pen = (0, lam, .., lam).  From w = 0, for it = 1, 2, ..:
  *   eta_i = w_0 + sum_{j = 1 .. P} z_ij w_j, in ascending j, starting from w_0.  ec_i = -700 if eta_i < -700, 700 if eta_i > 700, else eta_i
@@ -930,6 +930,79 @@ int mmm_classify_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P]
                            double* scores /* [R][L][D] or NULL */, int64_t* u2_obs /* [R][L] or NULL */, int64_t* s_obs /* [L] */,
                            double* coef /* [L][Q] or NULL */, int32_t* full_iters /* [L][2] or NULL */, uint32_t* ge, uint32_t* gemax /* [L] each */,
                            int64_t* maxstat /* [B] or NULL */, uint32_t* events /* [4] */);
+
+/* ---- a censored outcome against the exposures together: the cross-validated concordance index (Harrell's C) of a ridge-penalised,
+ * stratified Cox regression (Breslow ties, no intercept) on P features over D samples, for L penalties, with B permutations of the feature
+ * rows (within strata); the maximum over the penalties is permuted with the rest, so the p-value of the best penalty covers its choice (no
+ * counterpart in the reference).
+ * x [D][P]: a sample's features, as given (the Python layer standardises them).  time [D], finite and >= 0; event [D] in {0, 1} (1 = the
+ * event was seen at time, 0 = censored there).  strata [D] or NULL; s_i = strata[i], or 0.  fold [R][D]: the fold (< F) of sample i in
+ * repeat r, formed by the caller.  lambda [L], each > 0 and finite.  Q = P coefficients, no intercept.
+ * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
+ *   second Philox counter word 0xB0000000: bits 31, 29 and 28 without bit 30 are set by no other user of these words
+ *   (mmm_extract_signatures uses 0x80000000 | j with j < 32, mmm_classify_exposures 0x90000000, mmm_survival_association 0xA0000000,
+ *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_associate_exposures 0xE0000000, all others an index below 2^31).  Sample i keeps
+ *   its time, event, folds and stratum and receives the feature row x[pi(i)].  The outcome is not permuted: everything in the next three
+ *   paragraphs is the same for every replicate, and the host forms it once.  The identity replicate uses pi = id.
+ * Time order.  Positions q = 0 .. D-1 hold the samples in ascending (s_i, -time_i, i): within a stratum by descending time, ties by
+ *   ascending index (IEEE comparisons: -0.0 equals 0.0).  A tie group is a maximal run of positions with one stratum and one time; the
+ *   groups are numbered g = 0 .. NG-1 in position order, whether they hold an event or not.  The risk set of a group is every position of
+ *   its stratum from the stratum's first through the group's last.  Chunks: a stratum's positions are cut into chunks of 16 consecutive
+ *   positions counted from the stratum's first position (its last chunk may be shorter); NC chunks in all.
+ * One fit (T, lam), T a set of samples.  z_q = x[pi(i)] for the sample i at position q.  From w = 0, for it = 1, 2, ..:
+ *   eta_q = sum_{j = 0 .. P-1} z_qj w_j in ascending j from 0.0.  ec = -700 if eta < -700, 700 if eta > 700, else eta (a NaN stays).
+ *   u_q = ar_exp(ec_q) (csrc/mmm_arith.h) for a sample of T, +0.0 for any other.
+ *   Down-scan, for the 1 + P entries v = u and v = u z_j (one product): in a chunk the partial at position q is the sequential sum from 0.0
+ *   of v over the chunk's positions up to q; a chunk's total is its last partial; the offset of a chunk is the sequential sum from 0.0 of
+ *   the totals of the earlier chunks of its stratum; S(q) = offset + partial (one addition).  S0 and S1_j are S of the two kinds of entry.
+ *   Group terms.  d_G = the events of T in group G.  For d_G > 0, at the group's last position e: r_G = (double)d_G / S0(e), zbar_Gj =
+ *   S1_j(e) / S0(e).  A group with d_G = 0 contributes nothing anywhere, no quotient is formed for it.
+ *   Up-scan.  rho_q = r_G at the last position of a group with d_G > 0, +0.0 at every other position.  Over the SAME chunks, backwards: the
+ *   partial at q is the sequential sum from 0.0 of rho over the chunk's positions from its last down to q; the offset of a chunk is the
+ *   sequential sum from 0.0 of the totals of the LATER chunks of its stratum, taken from the stratum's last chunk downwards; Hhat_q = offset
+ *   + partial: the Breslow cumulative hazard at the sample's time (the sum of r_G over the groups of the stratum with time <= its own).
+ *   Residuals.  For a sample of T: uh_q = u_q Hhat_q, M_q = (double)event_q - uh_q (at w = 0 the log-rank score of
+ *   mmm_survival_association, up to the order of the hazard sum).
+ *   g_j = lam w_j - sum_{q in T} M_q z_qj.  H_jk = (sum_{q in T} z_qj (uh_q z_qk)) - (sum_{G : d_G > 0} zbar_Gj ((double)d_G zbar_Gk)),
+ *   then + lam where j = k: the subtraction first, then the penalty; for j >= k.  The sums over q run in the stripe order of
+ *   mmm_classify_exposures taken over POSITIONS: position q belongs to stripe q mod 16, a stripe's sum runs over its members of T in
+ *   ascending q from 0.0, the 16 stripe sums are added in ascending stripe order from 0.0.  The sum over G runs in the same stripe order
+ *   over the group index g.  Every product, quotient and sum is rounded separately (no contraction).
+ *   Cholesky, both substitutions, w <- w - d and the stopping rule exactly as in mmm_classify_exposures with Q = P: status 2 if a radicand
+ *   is not > 0 or not finite (w is what it was before this iteration) or if a w_j is not finite (with that w); else status 0 if max_j |d_j|
+ *   <= tol; else status 1 if it = maxiter.  Division and square root are the IEEE correctly rounded ones.
+ * Scores and statistic.  For (b, r, l) and every fold f: fit (T = {i : fold[r][i] != f}, lambda[l]); s_i = eta (unclamped) under the final
+ *   w for every i with fold[r][i] = f.  An event sample i is comparable with j iff s_i = s_j as strata and (time_j > time_i, or time_j =
+ *   time_i and event_j = 0).  U2(b, r, l) = sum_{i : event_i = 1} sum_{j comparable with i} (2 [s_i > s_j] + [s_i = s_j]), a NaN comparing
+ *   false.  n_pairs = the number of comparable pairs.  S_b[l] = sum_r U2(b, r, l): the cross-validated C-index is S / (2 R n_pairs).
+ *   M_b = max_l S_b[l].  Integers all.  (In the order (stratum, time ascending, events first, index) the partners of an event sample are
+ *   one contiguous range that ends with its stratum; the host forms the ranges.)
+ * Outputs.  Under the identity, by the same device code (a launch whose blocks share the R L cells and the L all-sample fits): scores
+ *   [R][L][D] (or NULL), u2_obs [R][L] (or NULL), s_obs [L], n_pairs [1], and coef [L][P] with full_iters [L][2] = (iterations, status) (or
+ *   NULL each) of the fit on T = all samples per penalty.  ge[l] = #{b in this call : S_b[l] >= s_obs[l]}, gemax[l] = #{b : M_b >=
+ *   s_obs[l]}, maxstat [B] (or NULL) = M_b.  events [4] = the fits that ended with status 1 and with status 2 under the identity (the
+ *   all-sample fits included), then among the permutations of this call: counted, not raised.
+ * Consequences.  (a) Every output is the same bits on every run and under every `waves`.  (b) maxstat of a call with (b0, B) is a slice of
+ *   the call with (0, b0 + B); ge, gemax and events[2], events[3] of chunked calls add.  (c) B = 0: the identity outputs, n_pairs and events
+ *   are written, ge, gemax and maxstat are untouched, MMM_OK.  (d) scores, u2_obs, s_obs, n_pairs, coef, full_iters, events[0] and
+ *   events[1] are independent of B, b0, seed and stream.
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice, 4; else 1, 2, 4, 8 or 16).  Placement, no bit depends
+ *   on it: zbar and the chunk totals (8 (NG (P + 1) + NC (P + 2)) bytes) are held in LDS when the block then stays within 64 KiB, else in a
+ *   workspace per resident block in device memory, the grid capped so that the workspaces together stay within 256 MiB; the permuted rows
+ *   are held in LDS when the block, with zbar if it is there, still stays within 64 KiB, else every read goes through pi to memory.
+ * Limits: 2 <= D <= 4096, 1 <= P <= 64, 2 <= F <= 255, 1 <= R <= 64, 1 <= L <= 32, 0 <= strata[d] < D, b0 + B <= 2^31 - 1.
+ * MMM_ERR_ARG, nothing written and before a device is asked for: NULL pointers (ctx, x, time, event, fold, lambda, s_obs, n_pairs, events;
+ *   ge and gemax with B > 0), D < 2, P < 1, R < 1, F < 2, L < 1, B < 0, b0 < 0, b0 + B > 2^31 - 1, maxiter < 1, not tol >= 0, a lambda
+ *   that is not > 0 and finite, an x that is not finite, a time that is not finite or is negative, an event other than 0 or 1, a fold >= F,
+ *   a stratum outside 0 .. D-1, waves not one of 0, 1, 2, 4, 8, 16, a training set (r, f) without an event, n_pairs = 0.
+ *   MMM_ERR_UNSUPPORTED, with the figure and the limit in the message: D > 4096, P > 64, R > 64, F > 255, L > 32.  Not handled: Efron
+ *   ties, time-varying covariates, left truncation, L1 penalties.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_cox_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, const double* time /* [D] */, const uint8_t* event /* [D] */,
+                      const int32_t* strata /* [D] or NULL */, int R, int F, const uint8_t* fold /* [R][D] */, int L,
+                      const double* lambda /* [L] */, int maxiter, double tol, int B, int b0, uint64_t seed, uint32_t stream, int waves,
+                      double* scores /* [R][L][D] or NULL */, int64_t* u2_obs /* [R][L] or NULL */, int64_t* s_obs /* [L] */,
+                      int64_t* n_pairs /* [1] */, double* coef /* [L][P] or NULL */, int32_t* full_iters /* [L][2] or NULL */, uint32_t* ge,
+                      uint32_t* gemax /* [L] each */, int64_t* maxstat /* [B] or NULL */, uint32_t* events /* [4] */);
 
 #ifdef __cplusplus
 }

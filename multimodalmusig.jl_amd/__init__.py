@@ -26,6 +26,7 @@ from .cluster import SampleClusters, cluster_samples
 from .associate import ExposureAssociations, associate_exposures
 from .survival import GroupTest, KMCurve, SurvivalAssociations, kaplan_meier, survival_association, survival_scores
 from .classify import ExposureClassifier, classify_exposures
+from .cox import ExposureCoxModel, cox_exposures
 from .io import read_signatures_tsv
 from .utils import (PackedCorpus, format_counts_ctm, format_counts_lda, format_counts_mmctm, make_count_matrix, pack_lda,
                     pack_mm, read_counts_tsv, shard_documents)
@@ -40,4 +41,4 @@ __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_l
            "decompose_signatures", "decompose_search", "Decomposition", "SearchResult", "extract_signatures", "Extraction",
            "cluster_samples", "SampleClusters", "associate_exposures", "ExposureAssociations",
            "survival_association", "survival_scores", "kaplan_meier", "SurvivalAssociations", "GroupTest", "KMCurve",
-           "classify_exposures", "ExposureClassifier"]
+           "classify_exposures", "ExposureClassifier", "cox_exposures", "ExposureCoxModel"]

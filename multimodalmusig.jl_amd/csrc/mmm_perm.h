@@ -1,4 +1,4 @@
-// mmm_perm.h -- what the permutation tests share (assoc.hip, survival.hip, classify.hip): the doubled midranks the host forms, and the block-level sort
+// mmm_perm.h -- what the permutation tests share (assoc.hip, survival.hip, classify.hip, cox.hip): the doubled midranks the host forms, and the block-level sort
 // that builds a within-stratum permutation from Philox keys (include/mmmusig.h, mmm_associate_exposures, has the definition)
 #pragma once
 #include "mmm_philox.h"

@@ -28,7 +28,7 @@ constexpr int kSvMaxD = 4096, kSvMaxP = 256, kSvMaxQ = 256, kSvMaxStrata = 64;
 constexpr int kSvAutoWaves = 4;
 constexpr int kSvSeg = 4;                       // consecutive cuts of a lane in the scan
 constexpr size_t kSvLdsBlock = 160 * 1024;
-constexpr uint32_t kSvBits = 0xA0000000u;       // second counter word: bits 31 and 29 without bit 30 are set by no other user
+constexpr uint32_t kSvBits = 0xA0000000u;       // second counter word: bits 31 and 29 without bits 30 and 28 are set by no other user
 constexpr double kSvScale = 16777216.0;         // 2^24
 
 struct SvArgs {

@@ -646,6 +646,61 @@ int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr,
                       int maxiter, double tol, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */, int32_t* count_ge,
                       int32_t* count_zero, int8_t* status, int64_t* iters, double* rep_stat /* [B][T D] or NULL */);
 
+/* ---- did the exposures change between a tumour's two mutation sets (clonal / subclonal, early / late, primary / relapse)?  An exact
+ * permutation test per sample, in one call (no counterpart in the reference).  Two CSR corpora over the same D
+ * samples and V terms, cat and allowed as mmm_refit_exposures takes them; P, f, fit(A) with the order of its sums, ll(A) and u(A) are those
+ * of mmm_refit_exposures, unchanged.
+ * Per sample d.  n^a, n^b: the dense count vectors of the two corpora (duplicate terms summed); n = n^a + n^b the pooled vector; N_a, N_b,
+ *   N = N_a + N_b their totals; A = {c : allowed[d][c]} (allowed == NULL: the whole catalogue).
+ * Dealing.  Under H0 the two sets are draws from one mixture, so given the pooled counts the partition into sets of sizes N_a and N_b is a
+ *   uniform random subset -- whatever was fitted: no null model is needed.  The N pooled mutations are numbered i = 0 .. N - 1 in term order
+ *   of the DENSE pooled vector: with cum the inclusive prefix sums of n over v ascending, mutation i lies in the term v with
+ *   cum[v-1] <= i < cum[v].  The key of mutation i in replicate b (the GLOBAL index b0 + ..., so chunked calls are slices of one big call) is
+ *   k_i = u_i >> (32 - key_bits), u_i being output word i % 4 of the Philox4x32-10 block with the constants and the key (seed low, seed
+ *   high) of mmm_resample_counts and the counter (i / 4, 0xD0000000 | d, b, stream).  High nibble 0xD of the second counter word is set by
+ *   no other user of these words (mmm_extract_signatures 0x8, mmm_classify_exposures 0x9, mmm_survival_association 0xA, mmm_cox_exposures
+ *   0xB, mmm_cluster_samples 0xC | k, mmm_associate_exposures 0xE; the resampler, the split and the simulator keep that word below 2^31),
+ *   hence D <= 2^28, b < 2^31, stream < 2^31.  Set a of the replicate is the N_a mutations with the smallest (k_i, i) in lexicographic
+ *   order; n^{a,b}_v = the number of those in term v, n^{b,b} = n - n^{a,b}.  So sum_v n^{a,b}_v = N_a exactly, 0 <= n^{a,b}_v <= n_v, and
+ *   the arithmetic is integer throughout: the same arguments give the same bits on every run and under every launch geometry.
+ *   key_bits in 1 .. 32.  With 32 the tie-break by index acts with probability about N / 2^32 per replicate and is not corrected, like the
+ *   2^-32 resolution of the resampler.  SMALL VALUES ARE A TEST HOOK: they make ties at the threshold the rule, so that the tie path is
+ *   run thousands of times per call, and they are BIASED towards low indices (with key_bits = 2 a quarter of the mutations share each key
+ *   and the lowest indices of the threshold's group always win).  Callers pass 32.
+ * Statistic of a pair (x, y) of count vectors (observed: (n^a, n^b); replicate: (n^{a,b}, n^{b,b})).  (w^x, ll_x, u_x) = fit(A) on x with
+ *   f = x / N_a;  (w^y, ll_y, u_y) = fit(A) on y with f = y / N_b;  T = ll_x + ll_y (one rounding);  delta_c = |w^x_c - w^y_c| for c in A
+ *   (0 outside), delta_max = max_c delta_c.  Once per sample (w^0, ll_0, u_0) = fit(A) on n with f = n / N.  stat[d] = max(2 (T_obs - ll_0), 0).
+ *   Mutations on terms that no signature of A can produce drop out of all three log-likelihoods alike; unexplained[d] = u_0 reports them.
+ *   With ONE signature in A every fit is w = 1 and T is the same for every partition up to rounding: count_ge of such a sample says nothing.
+ * Counts over the B replicates of THIS call (the counts of chunked calls add):  count_ge[d] = #{b : T_b >= T_obs};  count_sig[d][c] =
+ *   #{b : delta_{c,b} >= delta_{c,obs}};  count_max[d][c] = #{b : delta_{max,b} >= delta_{c,obs}} (single-step Westfall-Young max-T over the
+ *   signatures of the sample; both 0 outside A).  p = (1 + count) / (B + 1) is the caller's.
+ * status[d] = 3: untestable (N_a = 0, N_b = 0 or A empty) -- every other output of the sample is 0, no replicate is run (the caller's p is
+ *   NaN); 0: tested.  w_a, w_b, w_pool [D][C]: w^x, w^y of the observed pair and w^0 (exactly 0 outside A).  iters[d]: the EM iterations of
+ *   all the sample's fits, the replicates' of this call included.  rep_stat (or NULL): [b D + d] = 2 (T_b - ll_0), NaN for status 3.
+ * The dealt counts, every weight, delta, count_sig, count_max, status and iters are decided by +, x, / and comparisons in a fixed order:
+ *   the same bits on every run, under every launch geometry and wherever the catalogue is read from (LDS, or L2 where a sample's rows do
+ *   not fit or under MMM_OFF_REFIT_LDS).  T, stat, count_ge and rep_stat pass through the device log (< 1 ulp per term), as ll of
+ *   mmm_refit_exposures does.
+ * Limits: 1 <= C <= 256, 1 <= V <= 4096, D <= 2^28, N_d < 2^31, b0 + B <= 2^31 - 1; B = 0 runs the observed phase only; D = 0 writes
+ *   nothing.  MMM_ERR_ARG, nothing written: NULL pointers, key_bits outside 1 .. 32, B < 0, b0 < 0, b0 + B > 2^31 - 1, stream >= 2^31,
+ *   maxiter < 1, tol < 0, either corpus not a CSR of terms < V, a negative count and the catalogue errors of mmm_refit_exposures.
+ *   MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256, V > 4096, D > 2^28, N_d >= 2^31.  No collective: on a multi-rank context
+ *   both act on their arrays. */
+/* The dealing alone, on ONE CSR corpus: mutations are numbered in CSR order of the entries, as mmm_split_counts numbers them, the counter
+ * is the one above, and out[b nnz + e] (b < B, nnz = doc_ptr[D]) is the part of entry e that goes to set a of replicate b0 + b, n_a[d] of
+ * the document's mutations in all.  For a corpus whose entries are in term order without duplicates this is the dealing above.
+ * Replicates go through a bounded device buffer in chunks.  B = 0 or nnz = 0: MMM_OK, nothing written.  MMM_ERR_ARG also for an n_a[d]
+ * outside [0, N_d]; no term array and no V limit here. */
+int mmm_deal_counts(mmm_ctx* ctx, int D, const int64_t* doc_ptr, const int32_t* count, const int32_t* n_a /* [D] */, int B, int b0, uint64_t seed,
+                    uint32_t stream, int key_bits, int32_t* out /* [B][nnz] */);
+int mmm_compare_exposures(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr_a, const int32_t* term_a, const int32_t* count_a,
+                          const int64_t* doc_ptr_b, const int32_t* term_b, const int32_t* count_b, const double* cat,
+                          const uint8_t* allowed /* [D][C] or NULL */, int B, int b0, uint64_t seed, uint32_t stream, int key_bits, int maxiter, double tol,
+                          double* w_a, double* w_b, double* w_pool /* [D][C] */, double* stat /* [D] */, int32_t* count_ge /* [D] */,
+                          int32_t* count_sig, int32_t* count_max /* [D][C] */, int8_t* status, double* unexplained, int64_t* iters /* [D] */,
+                          double* rep_stat /* [B][D] or NULL */);
+
 /* ---- signatures as sparse non-negative mixtures of catalogue rows: for every size s <= S the best subset of exactly s rows, by exhaustive
  * search (the step between extraction and assignment; no counterpart in the reference).
  * n signatures sig [n][V] and a catalogue cat [C][V], every entry finite and >= 0; rows need not be normalised.

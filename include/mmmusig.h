@@ -701,6 +701,66 @@ int mmm_compare_exposures(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_
                           int32_t* count_sig, int32_t* count_max /* [D][C] */, int8_t* status, double* unexplained, int64_t* iters /* [D] */,
                           double* rep_stat /* [B][D] or NULL */);
 
+/* ---- exposure trajectories: where along a tumour's ORDERED mutations (by cancer cell fraction, by inferred timing) do the exposures
+ * change, how many times, and is that more than chance?  Change points by optimal partitioning over a table of segment fits, and an exact
+ * permutation test of the best single cut, in one call (no counterpart in the reference).
+ * A CSR corpus of nbins BINS over V terms (doc_ptr [nbins + 1], term, count, as mmm_refit_exposures takes a corpus); bin_ptr [D + 1]: sample d
+ * owns the bins bin_ptr[d] .. bin_ptr[d+1] - 1 in timeline order, T = T_d their number.  cat and allowed as mmm_refit_exposures takes them;
+ * P, f, fit(A) with the order of its sums, ll(A) and u(A) are those of mmm_refit_exposures, unchanged.  L = min_len >= 1 (bins), M = max_cp >= 0.
+ * Per sample d, A = {c : allowed[d][c]} (allowed == NULL: the whole catalogue).
+ * Vectors.  n^t: the dense count vector of bin t (duplicate terms summed), N_t its total; c^t = sum_{s<t} n^s, c^0 = 0, c^T = n (the pooled
+ *   vector, total N); C_t the total of c^t.
+ * Segment table.  A segment (i, j), 0 <= i < j <= T, is the bins i .. j - 1; it is DEFINED when j - i >= L, and (0, T) is defined whatever L (a
+ *   timeline shorter than L is one segment).  For a defined segment, x = c^j - c^i, N_ij its total: (w^{ij}, ll_ij, u_ij) = fit(A) on x with
+ *   f = x / N_ij; N_ij = 0: w = 0, ll = 0, and no iteration is run.  Every defined segment is fitted exactly once.  seg_ll holds ll_ij at
+ *   index i T - i (i - 1) / 2 + (j - i - 1) of the sample's block, which starts at sum_{d'<d} T_d' (T_d' + 1) / 2; NaN where the segment is
+ *   not defined.
+ * Optimal partitioning (on the host, on the table: O(M T^2) additions a sample).  F_0(j) = ll_0j;  F_m(j) = max_i F_{m-1}(i) + ll_ij (one
+ *   rounding) over the i for which both are defined, i ascending, ties to the lowest i;  m <= min(M, max(floor(T / L) - 1, 0)).
+ *   best[d][m] = F_m(T), NaN where it is not defined (and for every larger m <= M).  n_cp[d] = the m that maximises
+ *   F_m(T) - (double)m * penalty[d] (one product, one subtraction) over the defined m, ties to the smallest m.  cp[d][k], k < n_cp, by
+ *   backtracking: the first bin of segment k + 1; -1 beyond.  w_seg[d][k][.], k <= n_cp: the weights w^{ij} of the chosen segments (exactly
+ *   0 outside A and in the rows beyond n_cp).  w_bin[bin][.] (or NULL): fit(A) on every bin alone.  Both are, bit for bit, what
+ *   mmm_refit_exposures with penalty == NULL gives on the same count vector (every fit is a cold start).
+ * Scan (T >= 2 L).  For the cuts t in [L, T - L]: G_t = ll_0t + ll_tT (one rounding, the values of the table); gain_cut[bin_ptr[d] + t] =
+ *   G_t - ll_0T, NaN for every other t; G_max = max_t G_t; cut[d] = the lowest t that attains it; stat[d] = max(2 (G_max - ll_0T), 0).
+ * Replicates.  Under H0 the exposures are constant along the timeline, so given the pooled counts the assignment of the N mutations to
+ *   bins of sizes N_0 .. N_{T-1} is uniform.  The keys are exactly those of mmm_compare_exposures' dealing for sample d: mutations numbered
+ *   in term order of the dense pooled vector, k_i from word i % 4 of the block with the counter (i / 4, 0xD0000000 | d, b, stream), b the
+ *   GLOBAL index b0 + ..., key_bits as there (callers pass 32).  With the mutations ordered by (k_i, i), the replicate's prefix vector
+ *   c^{t,b} counts, per term, the C_t smallest: it is what mmm_deal_counts gives for the pooled row with n_a = C_t under the same seed and
+ *   stream, and the prefixes of one replicate are nested because they share the keys.  (The tag is shared with the two-set test on
+ *   purpose, as mmm_presence_test shares the simulator's words: replicates can be reproduced through a shipped entry; a two-set test of
+ *   the same sample index under the same seed and stream is correlated with this one.)
+ *   G_{t,b} = ll(fit(A) on c^{t,b}) + ll(fit(A) on n - c^{t,b}) (a side without mutations: ll = 0, no iteration); G_{max,b} the maximum over
+ *   the same cuts.  count_ge[d] = #{b : G_{max,b} >= G_max};  count_cut[bin_ptr[d] + t] = #{b : G_{max,b} >= G_t}, the single-step max-T
+ *   adjusted count of cut t, 0 for every other t.  Both over the B replicates of THIS call (the counts of chunked calls add).
+ *   rep_stat (or NULL): [b D + d] = 2 (G_{max,b} - ll_0T), NaN for the samples that are not tested.
+ * status[d] = 3: N = 0 or A empty -- seg_ll, best and gain_cut of the sample are NaN, cp and cut -1, everything else 0;  1: T < 2 L -- table,
+ *   partitioning (n_cp = 0 necessarily) and weights are computed, there is no scan and there are no replicates (cut -1, stat 0, gain_cut
+ *   NaN, counts 0);  0: tested.  unexplained[d] = u_0T.  iters[d] = the EM iterations of the table's fits plus those of this call's
+ *   replicate fits; the fits that produce w_bin and w_seg are not counted.
+ * The dealt vectors, every weight, status, unexplained and iters are decided by +, x, / and comparisons in a fixed order: the same bits on
+ *   every run, under every launch geometry and wherever the catalogue is read from (LDS, or L2 where a sample's rows do not fit or under
+ *   MMM_OFF_REFIT_LDS).  seg_ll, best, gain_cut, stat, cut, n_cp, cp, the counts and rep_stat pass through the device log (< 1 ulp per
+ *   term), as ll of mmm_refit_exposures does; given seg_ll, the partitioning and the scan are exact double arithmetic in the order above.
+ *   With ONE signature in A every fit is w = 1 and every G is the same up to rounding: cut, the counts and the change points of such a
+ *   sample say nothing.
+ * Limits: 1 <= C <= 256, 1 <= V <= 4096, D <= 2^28, N_d < 2^31, b0 + B <= 2^31 - 1, T_d <= 128 (MMM_TRAJECTORY_MAX_BINS); B = 0 runs the
+ *   observed part only; D = 0 or nbins = 0 writes nothing.  MMM_ERR_ARG, nothing written: NULL pointers (cp may be NULL when max_cp = 0), a
+ *   bin_ptr that does not start at 0, decreases or does not end at nbins, min_len < 1, max_cp < 0, a penalty that is negative or not finite
+ *   and the argument errors of mmm_compare_exposures.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256, V > 4096, D > 2^28,
+ *   T_d > 128, N_d >= 2^31.  No collective: on a multi-rank context it acts on its arrays. */
+#define MMM_TRAJECTORY_MAX_BINS 128
+int mmm_exposure_trajectory(mmm_ctx* ctx, int D, int C, int V, int nbins, const int64_t* doc_ptr, const int32_t* term, const int32_t* count,
+                            const int64_t* bin_ptr /* [D + 1] */, const double* cat, const uint8_t* allowed /* [D][C] or NULL */, int min_len, int max_cp,
+                            const double* penalty /* [D] */, int B, int b0, uint64_t seed, uint32_t stream, int key_bits, int maxiter, double tol,
+                            double* seg_ll /* [sum_d T_d (T_d + 1) / 2] */, double* best /* [D][max_cp + 1] */, int32_t* n_cp /* [D] */,
+                            int32_t* cp /* [D][max_cp] */, double* w_seg /* [D][max_cp + 1][C] */, double* w_bin /* [nbins][C] or NULL */,
+                            double* gain_cut /* [nbins] */, int32_t* cut /* [D] */, double* stat /* [D] */, int32_t* count_ge /* [D] */,
+                            int32_t* count_cut /* [nbins] */, int8_t* status, double* unexplained, int64_t* iters /* [D] */,
+                            double* rep_stat /* [B][D] or NULL */);
+
 /* ---- signatures as sparse non-negative mixtures of catalogue rows: for every size s <= S the best subset of exactly s rows, by exhaustive
  * search (the step between extraction and assignment; no counterpart in the reference).
  * n signatures sig [n][V] and a catalogue cat [C][V], every entry finite and >= 0; rows need not be normalised.

@@ -154,6 +154,8 @@ _SIGS = {
     "mmm_deal_counts": (C.c_int, [vp, C.c_int, i64p, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, vp]),
     "mmm_compare_exposures": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, i64p, vp, vp, f64p, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int,
                                         C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_exposure_trajectory": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, vp, i64p, f64p, vp, C.c_int, C.c_int, f64p, C.c_int, C.c_int, C.c_uint64,
+                                          C.c_uint32, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_decompose_search": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_signature_decompose": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_extract_signatures": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, i64p, vp, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int,

@@ -95,7 +95,7 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_CTM_PIPE_GAUSS = 1 << 12,    /* Gaussian M-step: the three-barrier-per-column inversion instead of the pipelined one (sum K <= 32); same bits         */
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
     MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
-    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
+    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test / _power: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
     MMM_OFF_DECOMPOSE_LDS = 1 << 16,     /* mmm_decompose_search, mmm_signature_decompose: read G and b through L2 even where they fit LDS; same bits                        */
     MMM_OFF_ALL = (1 << 17) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
@@ -645,6 +645,49 @@ int mmm_presence_test(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr,
                       const uint8_t* allowed /* [D][C] or NULL */, int T, const int32_t* targets /* [T] */, int B, int b0, uint64_t seed, uint32_t stream,
                       int maxiter, double tol, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */, int32_t* count_ge,
                       int32_t* count_zero, int8_t* status, int64_t* iters, double* rep_stat /* [B][T D] or NULL */);
+
+/* ---- what is a negative of the presence test worth?  Its detection power per (target, document) over a grid of spiked-in fractions and
+ * totals, in one call (no counterpart in the reference).  Items, A0, A1, fit(A), the statistic Lambda, the score, the
+ * rule that skips fit(A1) and the statuses are those of mmm_presence_test, unchanged.
+ * Observed.  As mmm_presence_test: w0 = w_null[j][.], stat, score, w_alt, status per item j = t_idx D + d.  Items of status 3 (untestable)
+ *   take no part: every other output of theirs is 0 (rep_stat NaN; the caller's power is NaN).  Items of status 0, 1 AND 2 all take part --
+ *   an item with Lambda_obs = 0 is the main customer.
+ * Levels.  H totals x (1 + G) fractions: phi_0 = 0 (the null level), phi_g = fractions[g - 1] for g >= 1, strictly increasing in (0, 1];
+ *   level l = h (1 + G) + g, L = H (1 + G) of them.  The total of (h, d) is N^h_d = n_level[h D + d] (>= 1); n_level == NULL: H = 1 and the
+ *   observed N_d.
+ * Generating weights of (l, j).  W0 = the sequential sum of w0_c over c ascending.  For g >= 1: w^l_c = (1 - phi_g) * w0_c for c in A0,
+ *   w^l_t = phi_g * W0, 0 elsewhere ((1 - phi_g) one subtraction, each weight one product).  For g = 0: w^l = w0 itself, by definition and
+ *   not by a product with 1.
+ * Replicates.  Replicate b in [b0, b0 + B) of (l, j) is the vector mmm_simulate_counts gives for document l T D + j of an L T D-document
+ *   corpus whose props rows are the w^l_j, phi = P and n_doc = N^h_d, under the same (seed, stream): the mixture summed over all C in
+ *   ascending c, the sequential cum, T_v = floor((cum_v / S) 2^32), the counter (i / 4, l T D + j, 0x80000000 | b, stream).  So every
+ *   replicate can be reproduced through a shipped entry, and level 0 at the observed totals is word for word the replicate sequence of
+ *   mmm_presence_test.  Lambda^l_b is the statistic of that replicate over the same A0 and A1.
+ * Critical value.  m = floor(alpha * (B + 1)) - 1, the product one multiplication in double.  With s_1 >= s_2 >= ... the B null statistics
+ *   (g = 0) of (h, j): crit[h T D + j] = s_{m+1}; +inf where m < 0 (the test cannot reject at this B) and where m + 1 > B.  Rejection is
+ *   Lambda > crit, which is exactly "p = (1 + #{Lambda_null >= Lambda}) / (B + 1) <= alpha" of the presence test.  crit is an element of the
+ *   set: how it is selected cannot change its bits.
+ * Outputs.  crit [H][T D]; count_reject[l T D + j] = #{b : Lambda^l_b > crit[h][j]}; count_zero[l T D + j] = #{b : Lambda^l_b = 0};
+ *   iters[j]: the EM iterations of all the item's fits, every level's replicates of this call included; rep_stat (or NULL):
+ *   [(l B + b) T D + j] = Lambda^l_b, NaN for the levels and items without replicates.  At g = 0 count_reject <= max(m, 0) by construction:
+ *   the attained size of the test.
+ * crit_in (or NULL): [H][T D].  Given, the null levels (g = 0) are NOT run: crit = crit_in, the counts of the null levels are 0 and their
+ *   rep_stat is NaN; the other outputs are then a pure function of the replicates, and the counts of calls over (b0, B) chunks add.  Without
+ *   crit_in a call takes its critical values from the B null replicates of THIS call only, so its counts do not add over chunks.
+ * The draws, the branch taken in every replicate, count_zero and iters are decided as in mmm_presence_test: the same bits on every run, under
+ *   every launch geometry and wherever the catalogue is read from.  Lambda passes through the device log; crit is one of those values and
+ *   count_reject compares with it.  All counts are integers added by integer atomics.
+ * Limits: 1 <= C <= 256, 1 <= V <= 4096, T >= 1, 1 <= G <= 64, 1 <= H <= 64, L T D < 2^31, N_d < 2^31, b0 + B <= 2^31 - 1; D = 0 writes
+ *   nothing.  MMM_ERR_ARG, nothing written: NULL pointers, G < 1, H < 1, n_level == NULL with H != 1, an n_level entry < 1, alpha outside
+ *   (0, 1), fractions not strictly increasing or outside (0, 1], B < 0, B = 0 without crit_in, b0 < 0, b0 + B > 2^31 - 1 and every error of
+ *   mmm_presence_test.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256, V > 4096, G > 64, H > 64, L T D >= 2^31, N_d >= 2^31.
+ *   No collective: on a multi-rank context it acts on its arrays. */
+int mmm_presence_power(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                       const uint8_t* allowed /* [D][C] or NULL */, int T, const int32_t* targets /* [T] */, int G, const double* fractions /* [G] */, int H,
+                       const int32_t* n_level /* [H][D] or NULL */, double alpha, int B, int b0, uint64_t seed, uint32_t stream, int maxiter, double tol,
+                       const double* crit_in /* [H][T D] or NULL */, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */,
+                       int8_t* status, int64_t* iters, double* crit /* [H][T D] */, int32_t* count_reject, int32_t* count_zero /* [L][T D] */,
+                       double* rep_stat /* [L][B][T D] or NULL */);
 
 /* ---- did the exposures change between a tumour's two mutation sets (clonal / subclonal, early / late, primary / relapse)?  An exact
  * permutation test per sample, in one call (no counterpart in the reference).  Two CSR corpora over the same D

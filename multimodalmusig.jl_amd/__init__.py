@@ -20,6 +20,7 @@ from .select import (KPick, KSelection, MMSelection, ScoreResult, holdout, pick_
 from .refit import RefitIntervals, RefitResult, refit_exposures
 from .simulate import FitCheck, goodness_of_fit, simulate_counts
 from .presence import PresenceResult, signature_presence
+from .power import PowerResult, presence_power
 from .compare import ComparisonResult, compare_exposures, deal_counts
 from .trajectory import TrajectoryResult, bin_by_order, exposure_trajectory
 from .decompose import Decomposition, SearchResult, decompose_search, decompose_signatures
@@ -39,7 +40,7 @@ __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_l
            "cosine_similarity", "match_signatures", "match_restarts", "restart_consensus", "signature_consensus", "SignatureMatch", "ConsensusResult",
            "split_counts", "holdout", "score_exposures", "score_restarts", "pick_k", "select_num_signatures", "select_num_signatures_mmctm",
            "ScoreResult", "KPick", "KSelection", "MMSelection", "read_signatures_tsv", "refit_exposures", "RefitResult", "RefitIntervals",
-           "simulate_counts", "goodness_of_fit", "FitCheck", "signature_presence", "PresenceResult",
+           "simulate_counts", "goodness_of_fit", "FitCheck", "signature_presence", "PresenceResult", "presence_power", "PowerResult",
            "compare_exposures", "deal_counts", "ComparisonResult", "exposure_trajectory", "bin_by_order", "TrajectoryResult",
            "decompose_signatures", "decompose_search", "Decomposition", "SearchResult", "extract_signatures", "Extraction",
            "cluster_samples", "SampleClusters", "associate_exposures", "ExposureAssociations",

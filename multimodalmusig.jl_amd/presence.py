@@ -101,21 +101,8 @@ def _raw(ctx, D, V, doc_ptr, term, count, cat, targets, allowed=None, B=0, b0=0,
     return out
 
 
-def signature_presence(X, catalogue, targets, allowed=None, B=1000, seed=None, stream=0, b0=0, maxiter=1000, tol=1e-9, modality=None, keep_replicates=False,
-                       ctx=None):
-    """Per-sample test of H0: the weight of signature t is 0, for every t of `targets` and every sample of X -> PresenceResult.
-
-    X and catalogue as `refit_exposures` takes them (C <= 256; here also V <= 4096).  targets: catalogue rows, as indices or -- where the
-    catalogue has names -- as names.  allowed: as in `refit_exposures`, or a `RefitResult`, whose chosen sets are then used: refit first,
-    then test what was kept (is it significant?) or what was dropped (was it dropped for lack of evidence?).  A target is always ADDED to
-    the set for the larger fit and REMOVED from it for the null fit, whether the sample's set holds it or not.
-    B: parametric-bootstrap replicates per tested pair; p = (1 + #{Λ_b >= Λ_obs}) / (B + 1).  Pairs whose Λ_obs is exactly 0 (p = 1) or +inf
-    (p = 1 / (B + 1)) take no replicates.  Replicates b0 .. b0 + B - 1 of the sequence that (seed, stream) fixes: the counts of chunked
-    calls add.  seed is required when B > 0.  The replicates are the vectors `simulate_counts(exposures_null, P, N, B, seed, stream)` gives
-    for the T x D pairs as one corpus (P: the row-normalised catalogue), so a `goodness_of_fit` of the null fits under the same seed and
-    stream sees the same draws and is correlated with this test: give the two different streams.  The test is conservative: under H0
-    about half of the replicates (and of the samples) have Λ = 0 exactly, a point mass at p = 1.
-    keep_replicates: return the [B, T, D] statistics Λ_b.  ILDA / IMMCTM catalogues: TypeError (factorised tables)."""
+def _table(catalogue, targets, modality):
+    """-> (names or None, cat [C, V], int32 [T] targets, their names or None), within the limits of the presence kernels"""
     names, cat = _catalogue(catalogue, modality)
     C, V = cat.shape
     if C < 1 or V < 1:
@@ -125,10 +112,11 @@ def signature_presence(X, catalogue, targets, allowed=None, B=1000, seed=None, s
     if V > MAX_TERMS:
         raise ValueError("V = %d terms (limit %d)" % (V, MAX_TERMS))
     tg, tnames = _targets(targets, names, C)
-    B = int(B)
-    if B > 0 and seed is None:
-        raise ValueError("B > 0 replicates need a seed")
-    B, b0, seed, stream = _seeds(B, b0, 0 if seed is None else seed, stream)
+    return names, cat, tg, tnames
+
+
+def _corpus(X, modality, allowed, names, C, V):
+    """-> (D, doc_ptr, term, count, allowed [D, C] uint8 or None) of X as the presence kernels take it"""
     D = len(X)
     if _is_nested(X):
         if modality is None:
@@ -149,6 +137,31 @@ def signature_presence(X, catalogue, targets, allowed=None, B=1000, seed=None, s
         al = np.ascontiguousarray(allowed.active.T, dtype=np.uint8)
     else:
         al = _allowed(allowed, names, D, C)
+    return D, doc_ptr, term, count, al
+
+
+def signature_presence(X, catalogue, targets, allowed=None, B=1000, seed=None, stream=0, b0=0, maxiter=1000, tol=1e-9, modality=None, keep_replicates=False,
+                       ctx=None):
+    """Per-sample test of H0: the weight of signature t is 0, for every t of `targets` and every sample of X -> PresenceResult.
+
+    X and catalogue as `refit_exposures` takes them (C <= 256; here also V <= 4096).  targets: catalogue rows, as indices or -- where the
+    catalogue has names -- as names.  allowed: as in `refit_exposures`, or a `RefitResult`, whose chosen sets are then used: refit first,
+    then test what was kept (is it significant?) or what was dropped (was it dropped for lack of evidence?).  A target is always ADDED to
+    the set for the larger fit and REMOVED from it for the null fit, whether the sample's set holds it or not.
+    B: parametric-bootstrap replicates per tested pair; p = (1 + #{Λ_b >= Λ_obs}) / (B + 1).  Pairs whose Λ_obs is exactly 0 (p = 1) or +inf
+    (p = 1 / (B + 1)) take no replicates.  Replicates b0 .. b0 + B - 1 of the sequence that (seed, stream) fixes: the counts of chunked
+    calls add.  seed is required when B > 0.  The replicates are the vectors `simulate_counts(exposures_null, P, N, B, seed, stream)` gives
+    for the T x D pairs as one corpus (P: the row-normalised catalogue), so a `goodness_of_fit` of the null fits under the same seed and
+    stream sees the same draws and is correlated with this test: give the two different streams.  The test is conservative: under H0
+    about half of the replicates (and of the samples) have Λ = 0 exactly, a point mass at p = 1.
+    keep_replicates: return the [B, T, D] statistics Λ_b.  ILDA / IMMCTM catalogues: TypeError (factorised tables)."""
+    names, cat, tg, tnames = _table(catalogue, targets, modality)
+    C, V = cat.shape
+    B = int(B)
+    if B > 0 and seed is None:
+        raise ValueError("B > 0 replicates need a seed")
+    B, b0, seed, stream = _seeds(B, b0, 0 if seed is None else seed, stream)
+    D, doc_ptr, term, count, al = _corpus(X, modality, allowed, names, C, V)
     T = tg.size
     ctx = ctx or (catalogue.ctx if isinstance(catalogue, (LDA, MMCTM)) else _lib.default_context())      # every argument is checked before a device is asked for
     r = _raw(ctx, D, V, doc_ptr, term, count, cat, tg, al, B, b0, seed, stream, maxiter, tol, keep=bool(keep_replicates))

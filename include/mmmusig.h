@@ -95,7 +95,7 @@ enum { /* mmm_tuning_opts.disable: optimisations a test or an A/B run may switch
     MMM_OFF_CTM_PIPE_GAUSS = 1 << 12,    /* Gaussian M-step: the three-barrier-per-column inversion instead of the pipelined one (sum K <= 32); same bits         */
     MMM_OFF_CTM_SOLVE_ORDER = 1 << 13,   /* solve phase: a wave's slots take its documents in index order instead of longest-lambda-solve-of-the-previous-pass first; same bits */
     MMM_OFF_LDA_BLOCK_STATS = 1 << 14,   /* single-step E-step build: per-wave LDS slabs filled by ds_add_f64 (k_lda_estep) instead of the block product of k_lda_estep_block */
-    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test / _power: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
+    MMM_OFF_REFIT_LDS = 1 << 15,         /* mmm_refit_exposures, mmm_presence_test / _power, mmm_attribute_mutations: read the catalogue through L2 even where it (an item's rows) fits LDS; same bits       */
     MMM_OFF_DECOMPOSE_LDS = 1 << 16,     /* mmm_decompose_search, mmm_signature_decompose: read G and b through L2 even where they fit LDS; same bits                        */
     MMM_OFF_ALL = (1 << 17) - 1          /* every bit this build knows; mmm_ctx_set_tuning rejects others (and non-zero reserved fields) with MMM_ERR_ARG */
 };
@@ -688,6 +688,49 @@ int mmm_presence_power(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr
                        const double* crit_in /* [H][T D] or NULL */, double* w_null /* [T D][C] */, double* stat, double* score, double* w_alt /* [T D] */,
                        int8_t* status, int64_t* iters, double* crit /* [H][T D] */, int32_t* count_reject, int32_t* count_zero /* [L][T D] */,
                        double* rep_stat /* [L][B][T D] or NULL */);
+
+/* ---- which signature caused this mutation?  The posterior of every signature per queried (document, term) pair and its uncertainty by the
+ * non-parametric bootstrap, in one call (no counterpart in the reference).  CSR corpus, cat and allowed as
+ * mmm_refit_exposures takes them; P, n_v, N, f_v and fit(A) with the order of every sum are those of mmm_refit_exposures, unchanged.  No
+ * elimination runs here: A_d is the `allowed` row (NULL: the whole catalogue), normally the chosen set of an earlier refit.
+ * Queries.  A CSR over documents: q_ptr [D + 1] (from 0, not decreasing), Q = q_ptr[D]; q_term [Q], terms < V -- a queried term need not
+ *   occur in the document, and a (document, term) pair may be queried more than once; q_mult [Q] >= 1 or NULL = 1; q_group [Q] in [-1, G)
+ *   or NULL, -1 = no group.  A document without queries is not processed: status 4, its w row 0, no replicates.
+ * Observed.  w = fit(A_d).  q_v = sum_c w_c P[c][v], sequentially over c ascending.  For query e = (d, v): post[e][c] = (w_c * P[c][v]) / q_v
+ *   where q_v > 0, the product and the (IEEE, correctly rounded) division separate roundings; exactly 0 outside A_d; the whole row 0 where
+ *   q_v = 0.  w[d][.] is output too.  status[d]: 0 processed; 3: N_d = 0 or an empty `allowed` row -- every other output of the document
+ *   and of its queries is 0 and no replicates run; 4: no queries.
+ * Replicates (status 0).  Replicate b in [b0, b0 + B) of document d is EXACTLY the count vector mmm_resample_counts gives for (d, b, seed,
+ *   stream): the counter (i / 4, d, b, stream), r = (u N_d) >> 32, the inclusive prefix sums of the document's entries in CSR order, the
+ *   draws counted by term.  Deliberately so: the replicate can be reproduced through the shipped entry, and an attribution under the same
+ *   (seed, stream) uses the replicates of a bootstrap of the exposures (refit_exposures(bootstrap = B) in the Python layer), so the two
+ *   sets of intervals describe the same resamples.  Per replicate w_b = fit(A_d) on the replicate's counts (f_v = n_v / N_d) and
+ *   rho_b[e][c] is formed as post is.  With x = floor(rho_b * 2^24), an exact integer <= 2^24 (rho <= 1: q_v is a sum of non-negative
+ *   terms that holds the numerator):
+ *     sum_fx[e][c] += x;  sumsq_fx[e][c] += x * x;
+ *     top_count[e][c] += 1 for the c with the largest rho_b (ties: the lowest c), skipped where the replicate's q_v = 0;
+ *     void_count[e] += 1 where the replicate's q_v = 0;
+ *     group_fx[b - b0][g][c] += q_mult[e] * x for g = q_group[e] >= 0;
+ *     rep_post[b - b0][e][c] = rho_b (or NULL).
+ *   iters[d]: the EM iterations of all the document's fits in this call.
+ * No log is used anywhere: every output is decided by +, x, / and comparisons in a fixed order, and every accumulator is an integer added
+ *   by integer atomics, so the same arguments give the same bits on every run, under every launch geometry and wherever the catalogue is
+ *   read from (LDS, or L2 where an A_d's rows do not fit or under MMM_OFF_REFIT_LDS).  The counts and sums of calls with (b0, B) chunks
+ *   add; a call with (b0, B) is a slice of the call with (0, b0 + B).
+ * Limits: 1 <= C <= 256, 1 <= V <= 4096, N_d < 2^31, b0 + B <= 2^31 - 1, B <= 4096 per call (sumsq_fx cannot overflow and
+ *   mmm_replicate_summary takes rep_post; B = 0 runs the observed phase only), a QUERIED document has at most 4096 CSR entries (its
+ *   prefix sums are staged in LDS), the q_mult of a group sum to less than 2^31, Q < 2^31.  D = 0 or Q = 0: MMM_OK, nothing written.
+ *   MMM_ERR_ARG, nothing written: NULL pointers (group_fx may be NULL when G = 0, the replicate outputs when B = 0), a q_ptr that is no
+ *   CSR, a query term >= V, a mult < 1, a group outside [-1, G), G < 0, B < 0, b0 < 0, b0 + B > 2^31 - 1, maxiter < 1, tol < 0 and the
+ *   catalogue and corpus errors of mmm_refit_exposures.  MMM_ERR_UNSUPPORTED, with the limit in the message: C > 256, V > 4096,
+ *   N_d >= 2^31, B > 4096, a queried document with more than 4096 entries, a group whose mults reach 2^31, Q >= 2^31.  No collective: on a
+ *   multi-rank context it acts on its arrays. */
+int mmm_attribute_mutations(mmm_ctx* ctx, int D, int C, int V, const int64_t* doc_ptr, const int32_t* term, const int32_t* count, const double* cat,
+                            const uint8_t* allowed /* [D][C] or NULL */, const int64_t* q_ptr /* [D + 1] */, const int32_t* q_term,
+                            const int32_t* q_mult, const int32_t* q_group /* [Q]; mult / group or NULL */, int G, int B, int b0, uint64_t seed,
+                            uint32_t stream, int maxiter, double tol, double* w /* [D][C] */, double* post /* [Q][C] */, int8_t* status,
+                            int64_t* iters /* [D] */, uint64_t* sum_fx, uint64_t* sumsq_fx /* [Q][C] */, int32_t* top_count /* [Q][C] */,
+                            int32_t* void_count /* [Q] */, uint64_t* group_fx /* [B][G][C] */, double* rep_post /* [B][Q][C] or NULL */);
 
 /* ---- did the exposures change between a tumour's two mutation sets (clonal / subclonal, early / late, primary / relapse)?  An exact
  * permutation test per sample, in one call (no counterpart in the reference).  Two CSR corpora over the same D

@@ -21,6 +21,7 @@ from .refit import RefitIntervals, RefitResult, refit_exposures
 from .simulate import FitCheck, goodness_of_fit, simulate_counts
 from .presence import PresenceResult, signature_presence
 from .power import PowerResult, presence_power
+from .attribute import AttributionResult, attribute_mutations, mutation_table
 from .compare import ComparisonResult, compare_exposures, deal_counts
 from .trajectory import TrajectoryResult, bin_by_order, exposure_trajectory
 from .decompose import Decomposition, SearchResult, decompose_search, decompose_signatures
@@ -41,6 +42,7 @@ __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_l
            "split_counts", "holdout", "score_exposures", "score_restarts", "pick_k", "select_num_signatures", "select_num_signatures_mmctm",
            "ScoreResult", "KPick", "KSelection", "MMSelection", "read_signatures_tsv", "refit_exposures", "RefitResult", "RefitIntervals",
            "simulate_counts", "goodness_of_fit", "FitCheck", "signature_presence", "PresenceResult", "presence_power", "PowerResult",
+           "attribute_mutations", "AttributionResult", "mutation_table",
            "compare_exposures", "deal_counts", "ComparisonResult", "exposure_trajectory", "bin_by_order", "TrajectoryResult",
            "decompose_signatures", "decompose_search", "Decomposition", "SearchResult", "extract_signatures", "Extraction",
            "cluster_samples", "SampleClusters", "associate_exposures", "ExposureAssociations",

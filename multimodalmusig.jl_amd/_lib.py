@@ -153,6 +153,8 @@ _SIGS = {
                                     C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_presence_power": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_double, C.c_int, C.c_int,
                                      C.c_uint64, C.c_uint32, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_attribute_mutations": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, f64p, vp, i64p, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                          C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_deal_counts": (C.c_int, [vp, C.c_int, i64p, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, vp]),
     "mmm_compare_exposures": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64p, vp, vp, i64p, vp, vp, f64p, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int,
                                         C.c_int, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

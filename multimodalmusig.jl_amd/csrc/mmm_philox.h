@@ -1,5 +1,5 @@
 // mmm_philox.h -- the counter-based generator of the resampler (bootstrap.hip), the fold split (select.hip) and the starts of extract.hip,
-// and the categorical sampler built on it that simulate.hip and presence.hip share
+// the categorical sampler built on it that simulate.hip and presence.hip share, and the resampler's draw counted by term (attribute.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -82,5 +82,31 @@ __device__ __forceinline__ void draw_row(int lane, int P2, int z, uint32_t N, co
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (4u * i4 + (uint32_t)j < N) atomicAdd(&hist[z + pos[j]], (Hist)1);
+    }
+}
+
+// ---- the draw of mmm_resample_counts (bootstrap.hip, rs_draw_row_lds: the counter (i / 4, d, b, stream), r = (u N) >> 32, the first entry
+// e with cum[e] > r), counted by TERM: hist[eterm[e]] takes the draw that lands in entry e, so the wave leaves the replicate's dense count
+// vector (duplicate terms summed) where the resampler leaves the counts per entry.  cum[0..W): the document's inclusive prefix sums in CSR
+// order, cum[W-1] = N, padded with 0xffffffff to the power of two 2 * half >= W (half = 0 for W = 1); eterm[0..W): the entries' terms.
+template <class Hist>
+__device__ __forceinline__ void resample_row_terms(int lane, int half, uint32_t N, const uint32_t* cum, const int* eterm, Hist* hist, uint32_t d, uint32_t b,
+                                                   uint32_t stream, uint32_t k0, uint32_t k1)
+{
+    const uint32_t nblk = (N + 3u) >> 2;                       // N < 2^31
+    for (uint32_t i4 = (uint32_t)lane; i4 < nblk; i4 += 64u) {
+        uint32_t u[4], r[4];
+        int pos[4];
+        philox4x32_10(i4, d, b, stream, k0, k1, u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { r[j] = __umulhi(u[j], N); pos[j] = 0; }      // (u N) >> 32 < N
+        for (int step = half; step > 0; step >>= 1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (cum[pos[j] + step - 1] <= r[j]) pos[j] += step;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4u * i4 + (uint32_t)j < N) atomicAdd(&hist[eterm[pos[j]]], (Hist)1);     // cum[W-1] = N > r: pos <= W - 1
     }
 }

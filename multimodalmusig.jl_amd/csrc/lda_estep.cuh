@@ -295,15 +295,42 @@ __global__ __launch_bounds__(SINGLE ? kMaxWavesE * MMM_WAVE : 512, SINGLE ? 3 : 
 // it where the slab sums went.  The document groups start at chunk 0 (the rotation kept them off each other's slab entries): the four
 // documents of a wave instruction read the same table addresses, which broadcast.
 // A document that lists a term twice would write one sR cell twice: such corpora keep k_lda_estep (mmm_lda::block_stats, set at create).
-// LDS: [KP][V] table | [4 NW][16 ceil(V / 16)] r | [4 NW][KP] a.
+// LDS: [KP / 2][V][2] table | [2 NW][16 ceil(V / 16)][2] r | [4 NW][KP] a.
+// The table and r are held as PAIRS -- topics 2p, 2p + 1 of a term, documents 2p, 2p + 1 of a term slot, side by side in 16 bytes -- so that
+// every read of either is one ds_read_b128 (a wave's costs 4 LDS-array cycles; the ds_read2_b64 the compiler formed of two rows a stride
+// apart costs 8): a lane's term is KP / 2 reads whose 16 lanes cover 256 contiguous bytes, and the product takes two documents' r per read.
+constexpr int lda_pair_cell(int i, int v, int stride) { return ((i >> 1) * stride + v) * 2 + (i & 1); }
+constexpr int lda_tab_cell(int k, int v, int V) { return lda_pair_cell(k, v, V); }         // B_kv in sB
+constexpr int lda_r_cell(int d, int v, int Vs) { return lda_pair_cell(d, v, Vs); }         // r_dv in sR (d: the document's number in the block)
+// n rows (even) of `stride` cells: every (i, v) has a cell of its own inside the n * stride, and a pair starts on a 16-byte boundary
+constexpr bool pair_cells_fill(int n, int stride)
+{
+    bool seen[48 * 96] = {};
+    if (n % 2 || n * stride > 48 * 96) return false;
+    for (int i = 0; i < n; ++i)
+        for (int v = 0; v < stride; ++v) {
+            const int c = lda_pair_cell(i, v, stride);
+            if (c < 0 || c >= n * stride || seen[c]) return false;
+            if (c != lda_pair_cell(i & ~1, v, stride) + (i & 1) || lda_pair_cell(i & ~1, v, stride) % 2) return false;
+            seen[c] = true;
+        }
+    return true;
+}
+constexpr bool tab_cells_fill(int V) { for (int KP = 2; KP <= 12; KP += 2) if (!pair_cells_fill(KP, V)) return false; return true; }
+constexpr bool r_cells_fill(int V) { for (int NW : {1, 2, 3, 4, 12}) if (!pair_cells_fill(4 * NW, (V + 15) & ~15)) return false; return true; }      // waves per block
+static_assert(tab_cells_fill(5) && tab_cells_fill(50) && tab_cells_fill(96), "k_lda_estep_block's table: KP = 2 ... 12 topics as pairs");
+static_assert(r_cells_fill(5), "k_lda_estep_block's r: 4, 8, 12, 16 and 48 documents as pairs");
+static_assert(r_cells_fill(50), "k_lda_estep_block's r: 4, 8, 12, 16 and 48 documents as pairs");
+static_assert(r_cells_fill(96), "k_lda_estep_block's r: 4, 8, 12, 16 and 48 documents as pairs");
+
 template <int KP>
 __device__ __forceinline__ double lda_chunk_r(const int v, const double n, const bool act, const int V, const double (&av)[KP], double (&acc)[KP],
                                               const double* __restrict__ sB)
 {
-    const double* bcol = sB + v;
+    const double2* __restrict__ bcol = (const double2*)sB + v;      // lda_tab_cell(2 p, v, V) / 2 = p V + v
     double b[KP], s0 = 0.0, s1 = 0.0;
 #pragma unroll
-    for (int k = 0; k < KP; ++k) b[k] = bcol[k * V];
+    for (int k = 0; k < KP; k += 2) { const double2 p = bcol[(k / 2) * V]; b[k] = p.x; b[k + 1] = p.y; }
 #pragma unroll
     for (int k = 0; k + 1 < KP; k += 2) { s0 = fma(av[k], b[k], s0); s1 = fma(av[k + 1], b[k + 1], s1); }
     if (KP & 1) s0 = fma(av[KP - 1], b[KP - 1], s0);
@@ -336,10 +363,10 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     const int NW = blockDim.x >> 6, ND = NW * G;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int g = lane / L, l = lane % L;
-    double* sB = smem;                                   // [KP][V] exp(Elnbeta_{t-1})
-    double* sR = sB + (size_t)KP * V;                    // [ND][Vs] r_dv = n_dv / sum_k a_dk B_kv (0: term absent, document past D)
+    double* sB = smem;                                   // [KP / 2][V][2] exp(Elnbeta_{t-1}), lda_tab_cell
+    double* sR = sB + (size_t)KP * V;                    // [ND / 2][Vs][2] r_dv = n_dv / sum_k a_dk B_kv (0: term absent, document past D), lda_r_cell
     double* sA = sR + (size_t)ND * Vs;                   // [ND][KP] a_dk
-    double* myR = sR + (size_t)(wid * G + g) * Vs;
+    double* myR = sR + lda_r_cell(wid * G + g, l, Vs);   // the document's r_v at myR[2 (v - l)]: the lane's own slots are immediates away
     double* myA = sA + (size_t)(wid * G + g) * KP;
 
     // ---- every start-up load leaves here, in one group behind the stop flag's: a (or gamma), the table, the document's row.  Unconditional,
@@ -384,8 +411,14 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     if (l < KP) myA[l] = al;
     if (lda_stop_now(stop)) return;            // a previous pass met the stopping rule: this launch must not touch the state
 #pragma unroll
-    for (int q = 0; q < TB; ++q) { const int i = tid + q * (int)blockDim.x; if (i < KP * V) sB[i] = (i < K * V) ? tb[q] : 0.0; }
-    for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) sB[i] = (i < K * V) ? io.eB[i] : 0.0;      // (waves_per_block pinned below 4)
+    for (int q = 0; q < TB; ++q) {
+        const int i = tid + q * (int)blockDim.x, k = VT ? i / VT : i / V;      // entry i = k V + v of the topic-major table in memory
+        if (i < KP * V) sB[lda_tab_cell(k, i - k * V, V)] = (i < K * V) ? tb[q] : 0.0;
+    }
+    for (int i = tid + TB * (int)blockDim.x; i < KP * V; i += blockDim.x) {      // (waves_per_block pinned below 4)
+        const int k = VT ? i / VT : i / V;
+        sB[lda_tab_cell(k, i - k * V, V)] = (i < K * V) ? io.eB[i] : 0.0;
+    }
     __syncthreads();
     MMM_STAMP(2);
     if (!ext && valid && l < K) io.Eln[(size_t)d * K + l] = el;
@@ -405,8 +438,8 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
         if (j < nchmax) {
             const bool act = tv[j] >= 0;
             const double r = lda_chunk_r<KP>(act ? tv[j] : 0, tn[j], act, V, av, acc, sB);
-            if (drows) myR[j * L + l] = r;             // every slot of the row, zeros included (slots past V are never read)
-            else if (act) myR[tv[j]] = r;
+            if (drows) myR[2 * (j * L)] = r;           // every slot of the row, zeros included (slots past V are never read)
+            else if (act) myR[2 * (tv[j] - l)] = r;
         }
     }
     MMM_STAMP(4);
@@ -422,19 +455,22 @@ __global__ __launch_bounds__(kMaxWavesE * MMM_WAVE, 3) void k_lda_estep_block(Es
     double* out = EstepPass<RB>::partial(a, K);
     for (int i = tid; i < (KP / 2) * V; i += blockDim.x) {
         const int kp = VT ? i / VT : i / V, v = i - kp * V, k = 2 * kp;
-        const double* rc = sR + v;
+        const double2* __restrict__ rc = (const double2*)sR + v;      // lda_r_cell(2 p, v, Vs) / 2 = p Vs + v: documents 2 p, 2 p + 1
         const double* ac = sA + k;
+        const double2 bb = ((const double2*)sB)[kp * V + v];          // lda_tab_cell(k, v, V) / 2: B_kv, B_(k+1)v
         double t0 = 0.0, t1 = 0.0;
 #pragma unroll 2
         for (int dd = 0; dd < ND; dd += G) {
             double rr[G], a0[G], a1[G];
 #pragma unroll
-            for (int q = 0; q < G; ++q) { rr[q] = rc[(size_t)(dd + q) * Vs]; a0[q] = ac[(dd + q) * KP]; a1[q] = ac[(dd + q) * KP + 1]; }
+            for (int q = 0; q < G; q += 2) { const double2 p = rc[(size_t)((dd + q) >> 1) * Vs]; rr[q] = p.x; rr[q + 1] = p.y; }
+#pragma unroll
+            for (int q = 0; q < G; ++q) { a0[q] = ac[(dd + q) * KP]; a1[q] = ac[(dd + q) * KP + 1]; }
 #pragma unroll
             for (int q = 0; q < G; ++q) { t0 = fma(a0[q], rr[q], t0); t1 = fma(a1[q], rr[q], t1); }
         }
-        if (k < K) out[k * a.pstride + v] = sB[k * V + v] * t0;
-        if (k + 1 < K) out[(k + 1) * a.pstride + v] = sB[(k + 1) * V + v] * t1;
+        if (k < K) out[k * a.pstride + v] = bb.x * t0;
+        if (k + 1 < K) out[(k + 1) * a.pstride + v] = bb.y * t1;
     }
     MMM_STAMP(7);
 }

@@ -1205,6 +1205,50 @@ int mmm_cox_exposures(mmm_ctx* ctx, int D, int P, const double* x /* [D][P] */, 
                       int64_t* n_pairs /* [1] */, double* coef /* [L][P] or NULL */, int32_t* full_iters /* [L][2] or NULL */, uint32_t* ge,
                       uint32_t* gemax /* [L] each */, int64_t* maxstat /* [B] or NULL */, uint32_t* events /* [4] */);
 
+/* ---- exposures against covariates with continuous adjusters: the Freedman-Lane permutation test of a linear model (Freedman & Lane 1983;
+ * Winkler et al. 2014), P features against C tested covariates given A adjuster columns over D samples, B permutations of the reduced model's
+ * residual rows (within strata), with the per-covariate maximum for Westfall-Young max-T adjustment (no counterpart in the reference;
+ * DESIGN.md section 4.27).  The caller forms the linear algebra once: qz [D][A], an orthonormal basis of the adjustment space, intercept
+ * included (NULL iff A == 0); e [D][P], the features' residuals on that basis; w [D][Q], per tested covariate c its cols[c] >= 1 orthonormal
+ * columns spanning the covariate residualised on qz (one column for a numeric or binary covariate, G - 1 for G levels), in covariate order,
+ * Q = the sum of cols.  The library checks shapes and finiteness, not orthogonality: the outputs are what the formulas below give.
+ * Permutation of replicate b (GLOBAL index b0 + b): pi exactly as in mmm_associate_exposures (slot, key and e lists, ties by d), with the
+ *   second Philox counter word 0xF0000000: bits 31, 30, 29 and 28 together are set by no other user of these words (mmm_extract_signatures
+ *   uses 0x80000000 | j with j < 32, mmm_classify_exposures 0x90000000, mmm_survival_association 0xA0000000, mmm_cox_exposures 0xB0000000,
+ *   mmm_cluster_samples 0xC0000000 | k with k <= 32, mmm_deal_counts 0xD0000000 | d, mmm_associate_exposures 0xE0000000, all others an
+ *   index below 2^31).  Slot i keeps its design rows qz[i], w[i] and its stratum and receives the residual row e[pi(i)].  The identity
+ *   replicate uses pi = id.
+ * Dot products.  dot(f, g) over the slots i = 0 .. D-1 runs in the stripe order of mmm_extract_signatures and mmm_classify_exposures: slot
+ *   i belongs to stripe i mod 16; a stripe's sum runs over its slots in ascending i, from 0.0, over the separately rounded products
+ *   f_i g_i; the 16 stripe sums are added in ascending stripe order, from 0.0.  Nothing is contracted.
+ * Per feature p.  ss_p = dot(e[.][p], e[.][p]) in the identity order, formed once per call and used by every replicate.
+ *   a_j = dot(qz[.][j], e[pi(.)][p]).  rz = ss_p - (the sum over j = 0 .. A-1, ascending, from 0.0, of a_j a_j).
+ * Per covariate c.  u_q = dot(w[.][q], e[pi(.)][p]).  num = the sum over the columns q of c, ascending, from 0.0, of u_q u_q.
+ *   t[p][c] = num / rz if rz > 0, else +0.0 (a constant or fully explained feature gets p = 1).  Every product, sum and quotient is rounded
+ *   separately.  t is the partial R^2 of c given the adjusters; the partial F, (t / cols_c) / ((1 - t) / (D - A - cols_c)), is monotone in t
+ *   at fixed degrees of freedom, so the permutation p-values are those of F, and t of different features is on one scale for max-T within
+ *   a covariate.
+ * Outputs.  obs [P][C], u_obs [P][Q] (or NULL) and rz_obs [P] (or NULL): t, u and rz of the identity replicate, by a launch of the same
+ *   kernel.  ge[p][c] = #{b in this call : t_b[p][c] >= obs[p][c]}, IEEE comparisons.  M_b[c] = max_p t_b[p][c], within a covariate only.
+ *   ge_max[p][c] = #{b : M_b[c] >= obs[p][c]}.  maxstat [B][C] (or NULL) = M_b[c].
+ *   Consequences.  (a) Every output is the same bits on every run and under every `waves`, wherever the kernel holds its operands.
+ *   (b) maxstat of a call with (b0, B) is a slice of the call with (0, b0 + B).  (c) ge and ge_max of chunked calls add.  (d) obs, u_obs and
+ *   rz_obs do not depend on B, b0, seed or stream.  (e) If every stratum has one member, every pi is the identity and ge = ge_max = B.
+ * waves: the waves of a block, a pinned geometry for tests (0 = the library's choice; else 1, 2, 4, 8 or 16).
+ * Limits: 1 <= D <= 4096, 1 <= P <= 64, 0 <= A <= 32, 1 <= C, Q <= 64, D - A - cols[c] >= 1 for every c, b0 + B <= 2^31 - 1,
+ *   0 <= strata[d] < D.  Every entry of e, qz and w is finite with |v| <= 1e70, which keeps every product, square and sum of the
+ *   definition finite (4096 products below 1e140, u below 1e144, u u below 1e288), so no NaN arises and the maxima are plain.
+ * MMM_ERR_ARG, nothing written and before a device is asked for: NULL pointers (ctx, e, cols, w, obs; qz with A > 0; ge and ge_max with
+ *   B > 0), D < 1, P < 1, C < 1, A < 0, a cols[c] < 1, D - A - cols[c] < 1, B < 0, b0 < 0, b0 + B > 2^31 - 1, an entry of e, qz or w that is
+ *   not finite or beyond 1e70 in magnitude (its row and column are in the message), a stratum out of range, waves not one of 0, 1, 2, 4, 8, 16.  MMM_ERR_UNSUPPORTED,
+ *   with the figure and the limit in the message: D > 4096, P > 64, A > 32, Q > 64.  B = 0: obs, u_obs and rz_obs are written, the counts
+ *   are untouched, MMM_OK.  No collective: on a multi-rank context it acts on its arrays. */
+int mmm_regress_exposures(mmm_ctx* ctx, int D, int P, const double* e /* [D][P] */, int A, const double* qz /* [D][A] or NULL when A = 0 */,
+                          int C, const int32_t* cols /* [C], each >= 1 */, const double* w /* [D][Q], Q = sum cols */,
+                          const int32_t* strata /* [D] or NULL */, int B, int b0, uint64_t seed, uint32_t stream, int waves,
+                          double* obs /* [P][C] */, double* u_obs /* [P][Q] or NULL */, double* rz_obs /* [P] or NULL */, uint32_t* ge,
+                          uint32_t* ge_max /* [P][C] each */, double* maxstat /* [B][C] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

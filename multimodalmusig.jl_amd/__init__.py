@@ -28,6 +28,7 @@ from .decompose import Decomposition, SearchResult, decompose_search, decompose_
 from .extract import Extraction, extract_signatures
 from .cluster import SampleClusters, cluster_samples
 from .associate import ExposureAssociations, associate_exposures
+from .regress import ExposureRegressions, regress_exposures
 from .survival import GroupTest, KMCurve, SurvivalAssociations, kaplan_meier, survival_association, survival_scores
 from .classify import ExposureClassifier, classify_exposures
 from .cox import ExposureCoxModel, cox_exposures
@@ -45,6 +46,6 @@ __all__ = ["ILDA", "IMMCTM", "MMCTM", "LDA", "fit", "fit_bang", "format_counts_l
            "attribute_mutations", "AttributionResult", "mutation_table",
            "compare_exposures", "deal_counts", "ComparisonResult", "exposure_trajectory", "bin_by_order", "TrajectoryResult",
            "decompose_signatures", "decompose_search", "Decomposition", "SearchResult", "extract_signatures", "Extraction",
-           "cluster_samples", "SampleClusters", "associate_exposures", "ExposureAssociations",
+           "cluster_samples", "SampleClusters", "associate_exposures", "ExposureAssociations", "regress_exposures", "ExposureRegressions",
            "survival_association", "survival_scores", "kaplan_meier", "SurvivalAssociations", "GroupTest", "KMCurve",
            "classify_exposures", "ExposureClassifier", "cox_exposures", "ExposureCoxModel"]

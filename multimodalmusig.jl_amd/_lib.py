@@ -174,6 +174,8 @@ _SIGS = {
                                          C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mmm_cox_exposures": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64,
                                     C.c_uint32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mmm_regress_exposures": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, vp, vp, vp,
+                                        vp, vp, vp]),
 }
 
 

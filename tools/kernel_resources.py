@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CS = os.path.join(ROOT, "multimodalmusig.jl_amd", "csrc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -ffp-contract=off -Wno-unused-function -Wno-pass-failed".split()
 want = sys.argv[1:]
-for src in ("lda.hip", "ctm.hip", "p2p.hip", "bootstrap.hip", "match.hip", "select.hip", "refit.hip", "simulate.hip", "presence.hip", "compare.hip", "trajectory.hip", "decompose.hip", "extract.hip", "cluster.hip", "assoc.hip", "survival.hip", "classify.hip", "cox.hip"):
+for src in ("lda.hip", "ctm.hip", "p2p.hip", "bootstrap.hip", "match.hip", "select.hip", "refit.hip", "simulate.hip", "presence.hip", "compare.hip", "trajectory.hip", "decompose.hip", "extract.hip", "cluster.hip", "assoc.hip", "regress.hip", "survival.hip", "classify.hip", "cox.hip"):
     with tempfile.TemporaryDirectory() as td:
         r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", "-o", os.path.join(td, "x.s"), os.path.join(CS, src),
                             "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
